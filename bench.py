@@ -24,6 +24,12 @@ Weak scaling: per-GPU payloads and per-GPU device shard are fixed as N grows.
 
 Launch: ``python bench.py --gpus 1 --steps 200 --warmup 20`` or under torch.distributed.run
 for N > 1 (one rank per GPU, RCCL).
+
+A plain run does what the headline needs: set-up, warm-up, the timed steps, the result line.
+``--full`` adds the measurements that take runs of their own (the segment disks' write-bandwidth
+probe, ``detail.durable.disk_probe``).  The inputs are seeded and dated from a fixed epoch, so two
+runs with the same arguments process the same bytes; ``--dump-outputs DIR`` writes what the last
+timed step made durable (see :func:`dump_outputs`).
 """
 from __future__ import annotations
 
@@ -72,9 +78,14 @@ def parse():
     ap.add_argument("--durable-dir", default=os.environ.get("SW_DURABLE_DIR"),
                     help="segment directory, or a comma-separated list (one per disk): local rank r writes to "
                          "dirs[r %% len(dirs)] (default: a fresh directory under the temp dir, removed at exit)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: the disk probe (--disk-probe-mb)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's durable block (decoded rows in a canonical "
+                         "order, a seeded sample beyond 48 MB) and the timed steps' counters as DIR/<name>.npy")
     ap.add_argument("--disk-probe-mb", type=int, default=int(os.environ.get("SW_DISK_PROBE_MB", 256)),
-                    help="before timing, every rank writes this much with O_DIRECT + fdatasync to its segment "
-                         "directory at the same time: the node's aggregate disk bandwidth (0 = skip)")
+                    help="with --full: before timing, every rank writes this much with O_DIRECT + fdatasync to its "
+                         "segment directory at the same time: the node's aggregate disk bandwidth (0 = skip)")
     ap.add_argument("--durable-retention-gb", type=float, default=48.0,
                     help="oldest segment files beyond this are deleted (bounded disk use); 0 = keep all")
     ap.add_argument("--direct-io", action=argparse.BooleanOptionalAction, default=True)
@@ -90,14 +101,17 @@ def parse():
     ap.add_argument("--bus", action=argparse.BooleanOptionalAction, default=True,
                     help="GPU engine: consume raw batches from, and publish enriched batches to, commit-log "
                          "topics in place (pipeline/bus_io.py); --no-bus feeds pinned batches directly")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and not (args.durable and args.steps > 0):
+        ap.error("--dump-outputs writes the last timed step's durable block: it needs --durable and --steps > 0")
+    return args
 
 
 def durable_dirs(args) -> list[str]:
     return [d for d in (args.durable_dir or "").split(",") if d]
 
 
-def open_durable(args, rank, dev):
+def open_durable(args, rank, dev, step_bytes):
     """(directory to remove at exit or None, DurableEventStore, boot id) of this rank's segments.
     With several ``--durable-dir`` entries (one per disk) local rank r uses entry r mod n."""
     from sitewhere_amd.persistence.segments import DurableEventStore
@@ -109,15 +123,24 @@ def open_durable(args, rank, dev):
     if os.path.exists(seg_dir) and base:
         shutil.rmtree(seg_dir)
     retention = int(args.durable_retention_gb * (1 << 30))
+    # the ranks sharing a directory share its disk: each uses at most half its free space / sharers
+    local = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+    sharers = max(1, -(-local // max(1, len(dirs)))) if dirs else local
+    probe = os.path.abspath(tmpdir)
+    while not os.path.exists(probe):
+        probe = os.path.dirname(probe)
+    share = shutil.disk_usage(probe).free // (2 * sharers)
     if retention:
-        # the ranks sharing a directory share its disk: each keeps at most half its free space / sharers
-        local = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
-        sharers = max(1, -(-local // max(1, len(dirs)))) if dirs else local
-        probe = os.path.abspath(tmpdir)
-        while not os.path.exists(probe):
-            probe = os.path.dirname(probe)
-        free = shutil.disk_usage(probe).free
-        retention = max(2 << 30, min(retention, free // (2 * sharers)))
+        retention = max(2 << 30, min(retention, share))
+    # Warm-up of the disk, untimed: the first write to space the file system has never held runs well
+    # below the disk's rate (measured on fresh machines: the first run, and every run that writes
+    # further than the runs before it, waited for the disk), and the steps need about that rate.  So
+    # the space the run's segments will take is written once and freed before the store opens: about
+    # a quarter of a step's payload bytes reach the disk as its block, budgeted at half, and never
+    # more than retention keeps.
+    touch = min((args.steps + args.warmup) * step_bytes // 2, retention or share, share)
+    if touch >= 4 << 20:
+        disk_probe(seg_dir, touch >> 20, args.direct_io)
     # the store is indexed in the timed region: every block carries its index trailer, built on the
     # MI355X in the step that encodes it (alternate ids, assignment zone maps, customer / area / asset
     # key tables; csrc/include/swindex.h) and written with the block in the same group commit
@@ -135,7 +158,8 @@ def open_durable(args, rank, dev):
 def disk_probe(directory: str, mb: int, direct: bool = True) -> float:
     """Write ``mb`` MiB in 4 MiB O_DIRECT writes (page-aligned buffer) to a scratch file in
     ``directory``, fdatasync, remove it; returns GB/s.  Run by every rank at once (between barriers),
-    so the sum over a node's ranks is the node's aggregate bandwidth to its segment directories."""
+    so the sum over a node's ranks is the node's aggregate bandwidth to its segment directories.
+    Also the disk's warm-up (:func:`open_durable`): the space written stays touched once freed."""
     import mmap
     os.makedirs(directory, exist_ok=True)
     path = os.path.join(directory, f".disk-probe-{os.getpid()}")
@@ -208,6 +232,47 @@ def zone_polys(n, lat0, lon0, span, rng):
     return zones, tests
 
 
+DUMP_BYTES = 48 << 20      # of row columns per dump (the counters beside them are a few hundred bytes)
+
+
+def dump_outputs(directory: str, store, eng, counters: dict):
+    """What the timed path handed its caller, as ``directory/<name>.npy`` (float64).
+
+    The path's product is the durable store: the rows of the last timed step's block, read back
+    from the segment file and decoded, one file per column.  Rule alerts and presence events are
+    appended to a block in the order their threads finish, and an engine numbers measurement names
+    as it first sees them, so the rows are put in a canonical order (sorted by every column) and
+    carry the name's 64-bit hash (``name_hash_hi`` / ``name_hash_lo``, 32 bits each) instead of its
+    id.  Beyond ``DUMP_BYTES`` a fixed seeded sample of the sorted rows is kept; ``summary`` holds
+    the row count, the rows kept and every column's sum over all rows.  ``counters`` are the
+    engine's counters over the timed steps (``counter_names.txt`` names them)."""
+    from sitewhere_amd.persistence.segments import decode_block
+    idx = store.seg.index()
+    ent = idx[int(np.argmax(idx["first_seq"]))]
+    c = decode_block(store.seg.read_block(ent), strings=False)
+    hashes = np.zeros(1 << 16, np.uint64)
+    for h, i in eng.intern_table().items():
+        hashes[i] = h
+    nh = hashes[c["name"]]
+    cols = {"etype": c["etype"], "assignment": c["asg"], "event_date": c["date"], "name_hash_hi": nh >> np.uint64(32),
+            "name_hash_lo": nh & np.uint64(0xFFFFFFFF), "level": c["level"], "flags": c["flags"], "v0": c["v0"],
+            "v1": c["v1"], "v2": c["v2"]}
+    cols = {k: v.astype(np.float64) for k, v in cols.items()}
+    order = np.lexsort(tuple(reversed(list(cols.values()))))
+    cols = {k: v[order] for k, v in cols.items()}
+    n = len(order)
+    keep = min(n, DUMP_BYTES // (8 * len(cols)))
+    sample = np.sort(np.random.default_rng(0).choice(n, keep, replace=False)) if keep < n else slice(None)
+    os.makedirs(directory, exist_ok=True)
+    for k, v in cols.items():
+        np.save(os.path.join(directory, k + ".npy"), v[sample])
+    np.save(os.path.join(directory, "summary.npy"),
+            np.array([n, keep] + [float(np.nansum(v)) for v in cols.values()], np.float64))
+    np.save(os.path.join(directory, "counters.npy"), np.array(list(counters.values()), np.float64))
+    with open(os.path.join(directory, "counter_names.txt"), "w") as f:
+        f.write("\n".join(counters) + "\n")
+
+
 def main():
     args = parse()
     import torch
@@ -276,7 +341,7 @@ def main():
     zones, tests = zone_polys(args.zones, spec.lat0, spec.lon0, spec.span_deg, rng)
     eng.set_zone_rules(zones, tests)
     # ---- pre-generated synthetic raw batches (this rank's ingest stream)
-    now0 = int(time.time() * 1000)
+    now0 = 1_700_000_000_000        # a fixed epoch: the same arguments give the same bytes, run after run
     batches = []
     for b in range(args.batches):
         raw, offs_b = gen_payloads(spec, args.msgs, now0 - 30_000, seed=1 + rank * 1000 + b)
@@ -405,7 +470,7 @@ def main():
             routed["jobs"] = routed.get("jobs", 0) + 1
 
         if args.durable:
-            tmpdir, store, boot = open_durable(args, rank, dev)
+            tmpdir, store, boot = open_durable(args, rank, dev, max_raw)
             # the store keeps no row whose id the filter has forgotten (the blocks in flight are the
             # slack; EngineConfig.filter_retention_rows accounts for the file being written)
             store.limit_retention_rows(cfg.filter_retention_rows(16 * cfg.rec_cap))
@@ -516,7 +581,7 @@ def main():
             runner.flush()
     else:
         if args.durable:        # host engines encode the same blocks on the CPU (swseg_encode)
-            tmpdir, store, boot = open_durable(args, rank, dev)
+            tmpdir, store, boot = open_durable(args, rank, dev, max_raw)
             # the store keeps no row whose id the filter has forgotten (the blocks in flight are the
             # slack; EngineConfig.filter_retention_rows accounts for the file being written)
             store.limit_retention_rows(cfg.filter_retention_rows(16 * cfg.rec_cap))
@@ -538,8 +603,10 @@ def main():
             if dur is not None:
                 dur["sink"].flush()
 
+    if args.dump_outputs and dur is None:
+        sys.exit("bench: --dump-outputs needs the durable path (the GPU engine writes blocks through the bus)")
     probe = None
-    if dur is not None and args.disk_probe_mb > 0:
+    if args.full and dur is not None and args.disk_probe_mb > 0:
         # every rank at once, between barriers: per-rank and node-aggregate O_DIRECT write bandwidth
         barrier()
         gbps = disk_probe(dur["store"].dir, args.disk_probe_mb, args.direct_io)
@@ -727,6 +794,8 @@ def main():
         }
     if read_stats is not None:
         detail["reads"] = read_stats          # this rank's query latencies while it ingested
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dur["store"], eng, {k: s1[k] - s0[k] for k in STAT_NAMES})
     if rank == 0:
         out = {
             "metric": "device_events_per_sec",

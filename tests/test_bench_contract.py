@@ -35,6 +35,37 @@ def test_bench_single_rank_json():
     assert d["config"]["durable"] and dd["all_durable"] and dd["rows"] == d["detail"]["persisted"]
     assert dd["bytes_per_event"] > 0 and dd["durable_bytes_per_s"] > 0 and dd["fdatasyncs"] >= 1
     assert d["detail"]["conservation"]["ok"]
+    assert dd["disk_probe"] is None                 # a plain run times its steps only; the probe needs --full
+
+
+def test_bench_dump_outputs_repeat(tmp_path):
+    """``--dump-outputs``: two runs with the same arguments write the same arrays (seeded inputs dated
+    from a fixed epoch), with or without ``--full``, which adds the disk probe to the result line."""
+    import numpy as np
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full", "--disk-probe-mb", "8"])):
+        # three batches: the host engines replay their batches unstamped, and a replay is all duplicates
+        r = subprocess.run([sys.executable, "bench.py", *SMALL, "--batches", "3", *extra,
+                            "--dump-outputs", str(tmp_path / name)],
+                           cwd=REPO, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append(_json_lines(r.stdout)[0])
+    assert runs[0]["detail"]["durable"]["disk_probe"] is None
+    assert runs[1]["detail"]["durable"]["disk_probe"]["rank0_gbps"] > 0
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    cols = {"etype", "assignment", "event_date", "name_hash_hi", "name_hash_lo", "level", "flags", "v0", "v1", "v2"}
+    assert {f[:-4] for f in files if f.endswith(".npy")} == cols | {"summary", "counters"}
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files if f.endswith(".npy")}
+    for k, v in a.items():
+        assert v.dtype == np.float64 and np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy")), equal_nan=True), k
+    # the rows of the last timed step's block, all kept at this size; the counters cover both timed steps
+    n = int(a["summary"][0])
+    assert 0 < n == int(a["summary"][1]) and all(len(a[k]) == n for k in cols)
+    names = (tmp_path / "a" / "counter_names.txt").read_text().split()
+    counters = dict(zip(names, a["counters"]))
+    assert counters["persisted"] == runs[0]["detail"]["persisted"] and counters["messages"] == 2 * 1500
+    assert set(np.unique(a["etype"])) <= set(range(8)) and a["name_hash_lo"].max() > 0
 
 
 @pytest.mark.slow
@@ -48,7 +79,7 @@ def test_bench_two_ranks_torchrun(tmp_path):
     s.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", *SMALL,
-                        "--durable-dir", f"{d1},{d2}", "--disk-probe-mb", "8"],
+                        "--full", "--durable-dir", f"{d1},{d2}", "--disk-probe-mb", "8"],
                        cwd=REPO, capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, OMP_NUM_THREADS="2"))
     assert r.returncode == 0, r.stderr[-3000:]
