@@ -1617,6 +1617,73 @@ __global__ __launch_bounds__(BLK) void k_zone_mask(SwEngineArgs a, ull* __restri
   if (threadIdx.x == 0) ztile[BID] = M.count;
 }
 
+// Pass 1b: measurement (threshold) tests.  One thread per row over k_zone_mask's tiles: a measurement
+// row whose name matches test m and whose value lies outside [lo, hi] (strict fp64 compares, so a
+// value on a bound or a NaN does not fire) sets bit n_tests + m of the row's mask.  The rule table
+// (<= 1.5 KB) is staged once in LDS and read with a wave-uniform index (broadcast); the tile's alert
+// count is reduced per wave in registers, then over the waves through LDS.  After k_zone_mask
+// (fresh == 0) it ORs into zmask and adds to ztile; without zone tests (fresh != 0) it writes both,
+// ztile = 0 for the tiles past n_ok included.
+__global__ __launch_bounds__(BLK) void k_mx_mask(SwEngineArgs a, ull* __restrict__ zmask, uint32_t* __restrict__ ztile,
+                                                 int fresh) {
+  __shared__ SwMxTest lm[ZONE_LDS_TESTS];
+  __shared__ uint32_t wsum[WAVES];
+  const int nz = a.n_tests < ZONE_LDS_TESTS ? (int)a.n_tests : ZONE_LDS_TESTS;
+  const int nm = a.n_mtests < ZONE_LDS_TESTS - nz ? (int)a.n_mtests : ZONE_LDS_TESTS - nz;
+  const int64_t c0 = *a.step_cursor0;
+  const uint32_t n = *a.n_ok;              // this step's persisted device events, from c0
+  const int64_t base = (int64_t)BID * TILE;
+  if (base >= n) {                       // tile past this step's rows (k_zone_mask zeroed it otherwise)
+    if (fresh && threadIdx.x == 0) ztile[BID] = 0;
+    return;
+  }
+  for (int t = threadIdx.x; t < nm; t += BLK) lm[t] = a.mtests[t];
+  __syncthreads();
+  // the tile's ring rows: one 64-bit modulo per thread, then a wrap compare per row; the loads of
+  // the four rows are issued together (types first, then name and value of the measurement rows)
+  const int64_t cap = a.store_cap;
+  const int64_t row0 = (c0 + base) % cap + threadIdx.x;
+  int64_t row[TILE_ITEMS];
+  uint8_t et[TILE_ITEMS];
+#pragma unroll
+  for (int k = 0; k < TILE_ITEMS; ++k) {
+    row[k] = row0 + (int64_t)k * BLK;
+    while (row[k] >= cap) row[k] -= cap;
+    et[k] = base + (int64_t)k * BLK + threadIdx.x < n ? a.s_etype[row[k]] : (uint8_t)0xff;
+  }
+  ull name[TILE_ITEMS];
+  double val[TILE_ITEMS];
+#pragma unroll
+  for (int k = 0; k < TILE_ITEMS; ++k) {
+    const bool mx = et[k] == SW_EV_MEASUREMENT;
+    name[k] = mx ? a.s_name[row[k]] : 0ull;
+    val[k] = mx ? a.s_v0[row[k]] : 0.0;
+  }
+  uint32_t cnt = 0;
+#pragma unroll
+  for (int k = 0; k < TILE_ITEMS; ++k) {
+    const int64_t j = base + (int64_t)k * BLK + threadIdx.x;
+    if (j >= n) continue;
+    ull m = 0;
+    if (et[k] == SW_EV_MEASUREMENT) {
+      for (int t = 0; t < nm; ++t)
+        if (lm[t].name_hash == name[k] && (val[k] < lm[t].lo || val[k] > lm[t].hi)) m |= 1ull << (nz + t);
+    }
+    if (fresh) zmask[j] = m;
+    else if (m) zmask[j] |= m;
+    cnt += (uint32_t)__popcll(m);
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) cnt += __shfl_down(cnt, d, 64);
+  if (lane_id() == 0) wsum[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int w = 0; w < WAVES; ++w) tot += wsum[w];
+    ztile[BID] = fresh ? tot : ztile[BID] + tot;
+  }
+}
+
 // Pass 2: write the alerts at their scanned offsets (stable, no global atomics).
 // Tile offsets from k_zone_mask's tile counts, reduced in the prologue (no scan dispatch); the last
 // tile stores the step's rule alerts as n_gen and, clamped, n_rule -- before k_presence appends to
@@ -1631,7 +1698,9 @@ __global__ __launch_bounds__(BLK) void k_zone_emit(SwEngineArgs a, const ull* __
     *a.n_gen = all;
     *n_rule = all < a.gen_cap ? all : (uint32_t)a.gen_cap;
   }
-  const int nt = a.n_tests < ZONE_LDS_TESTS ? (int)a.n_tests : ZONE_LDS_TESTS;
+  // zone tests, then the measurement tests' entries (one test-index space)
+  const int64_t nall = a.n_tests + a.n_mtests;
+  const int nt = nall < ZONE_LDS_TESTS ? (int)nall : ZONE_LDS_TESTS;
   for (int t = threadIdx.x; t < nt; t += BLK) {
     const SwZoneTest zt = a.tests[t];
     lt[t] = make_int4(zt.zone, zt.condition, zt.alert_name_id, zt.level);
@@ -2049,6 +2118,8 @@ int sw_phase_process(const SwEngineArgs* ap, uint32_t* scratch4, hipStream_t s) 
   if (2 * ntiles > a.scan_tmp_len) return -4;
   if (a.dd_ff && (a.dd_ff_gens < 2 || a.dd_ff_gens > SW_FF_MAX_GENS || !a.dd_ff_meta || a.dd_ff_bmask < 0))
     return -6;
+  // one fired bit per test: measurement tests need the whole index space inside the 64-bit mask
+  if (a.n_mtests < 0 || (a.n_mtests > 0 && (!a.mtests || a.n_tests + a.n_mtests > ZONE_LDS_TESTS))) return -7;
   k_lookup<<<g, BLK, 0, s>>>(a);         // + the phase's resets (block 0)
   if (a.dd_ff) k_ff_probe<<<g, BLK, 0, s>>>(a);
   k_dedup_claim<<<g, BLK, 0, s>>>(a);
@@ -2073,15 +2144,18 @@ int sw_phase_process(const SwEngineArgs* ap, uint32_t* scratch4, hipStream_t s) 
   k_state_p2<<<g, BLK, 0, s>>>(a, a.n_ok, (uint32_t)a.rec_cap, nullptr);
   // rules on this step's persisted locations, then presence scan; generated events persist too
   uint32_t* n_rule = scratch4;
-  if (a.n_tests > 0) {
+  if (a.n_tests + a.n_mtests > 0) {
     const int64_t otiles = (a.rec_cap + TILE - 1) / TILE;
     ull* zmask = (ull*)a.zmask;
     uint32_t* ztile = a.ztile;
-    const size_t vtx_bytes = zone_vtx_in_lds(a) ? (size_t)a.n_zone_vtx * 2 * sizeof(double) : 0;
-    k_zone_mask<<<(unsigned)otiles, BLK, vtx_bytes, s>>>(a, zmask, ztile);
+    if (a.n_tests > 0) {
+      const size_t vtx_bytes = zone_vtx_in_lds(a) ? (size_t)a.n_zone_vtx * 2 * sizeof(double) : 0;
+      k_zone_mask<<<(unsigned)otiles, BLK, vtx_bytes, s>>>(a, zmask, ztile);
+    }
+    if (a.n_mtests > 0) k_mx_mask<<<(unsigned)otiles, BLK, 0, s>>>(a, zmask, ztile, a.n_tests > 0 ? 0 : 1);
     k_zone_emit<<<(unsigned)otiles, BLK, 0, s>>>(a, zmask, ztile, n_rule);
   } else {
-    k_gen_clamp<<<1, 64, 0, s>>>(a, n_rule);        // no zone tests: n_rule = n_gen = 0
+    k_gen_clamp<<<1, 64, 0, s>>>(a, n_rule);        // no rules: n_rule = n_gen = 0
   }
   k_presence<<<grid_for(a.n_asg), BLK, 0, s>>>(a);   // exits at once when presence is off this step
   // consumers of the generated events clamp n_gen to gen_cap themselves; k_step_end stores it

@@ -154,9 +154,9 @@ typedef struct SwEngineArgs {
   const int32_t* zone_off;     // [n_zones + 1]
   const double* zone_bbox;     // [4 * n_zones] min_lat, min_lon, max_lat, max_lon
   int64_t n_zones;
-  const SwZoneTest* tests;
+  const SwZoneTest* tests;         // [n_tests + n_mtests]
   int64_t n_tests;
-  const uint64_t* test_name_hash; // alert type hash per test
+  const uint64_t* test_name_hash; // alert type hash per test [n_tests + n_mtests]
   uint64_t* zmask;             // [rec_cap] fired-test bitmask per persisted row
   uint32_t* ztile;             // [2 * ntiles] tile counts + scanned offsets
   // generated events (rule alerts, presence state changes)
@@ -235,6 +235,12 @@ typedef struct SwEngineArgs {
   uint8_t* spill_str;          // [carry_str_cap]
   uint32_t* n_spill_str;       // bytes of spill_str in use (k_part_counts)
   int64_t carry_str_cap;
+  // ---------------------------------------------------------------- rules (measurement tests)
+  // Test indices are one space: zone tests 0 .. n_tests - 1, measurement tests n_tests ..
+  // n_tests + n_mtests - 1 (at most 64 together); `tests` and `test_name_hash` hold the measurement
+  // tests' level / alert-type entries after the zone entries.
+  const SwMxTest* mtests;
+  int64_t n_mtests;
 } SwEngineArgs;
 
 #define SW_N_STATS 24

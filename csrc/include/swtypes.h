@@ -182,6 +182,14 @@ typedef struct SwZoneTest {
   int32_t level;        // alert level
 } SwZoneTest;
 
+// Measurement (threshold) test: fires on a measurement row when name_hash matches and
+// v0 < lo || v0 > hi (strict, fp64; an absent bound is -inf / +inf, a NaN value never fires).
+typedef struct SwMxTest {
+  uint64_t name_hash;   // hash of the measurement name
+  double lo;
+  double hi;
+} SwMxTest;
+
 // ---------------------------------------------------------------- hashing
 #define SW_FNV_OFFSET 0xcbf29ce484222325ULL
 #define SW_FNV_PRIME 0x100000001b3ULL

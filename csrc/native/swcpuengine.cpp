@@ -262,6 +262,11 @@ typedef struct SwCeTables {
   uint64_t* stats;  // [SW_N_STATS], SW_STAT_* slots
   int32_t cluster;  // persist each step stable-sorted by assignment (EngineConfig.cluster)
   int32_t pad0;
+  // measurement (threshold) tests: test indices n_tests .. n_tests + n_mtests - 1
+  const SwMxTest* mtests;
+  const int32_t* mtest_level;
+  const uint64_t* mtest_hash;
+  int64_t n_mtests;
 } SwCeTables;
 
 typedef struct SwCeStep {
@@ -747,17 +752,27 @@ int32_t swce_process(void* p, const SwCeTables* t, SwCeStep* st, const SwEventRe
   int64_t cursor = cursor0 + n_ok;
   lap("state");
 
-  // 7. zone-test rules over the persisted locations, generated in (row, test) order
+  // 7. rules over the persisted rows, generated in (row, test) order: zone tests on locations,
+  // measurement tests (indices n_tests ..) on measurements
   std::vector<SwEventRec> gen;
   std::vector<int32_t> gen_asg;
   int64_t n_rule = 0;
-  if (t->n_tests > 0) {
+  const int64_t n_all = (int64_t)t->n_tests + t->n_mtests;
+  if (n_all > 0) {
     e->pool.run([&](int w) {
       std::vector<int64_t>& hits = e->scratch64[w];
       hits.clear();
       int64_t b, end;
       chunk_of(n_ok, w, T, &b, &end);
       for (int64_t j = b; j < end; ++j) {
+        if (out[j].etype == SW_EV_MEASUREMENT) {
+          const SwEventRec& r = work[ok_idx[j]];
+          for (int64_t m = 0; m < t->n_mtests; ++m) {
+            const SwMxTest& mt = t->mtests[m];
+            if (mt.name_hash == r.name_hash && (r.v0 < mt.lo || r.v0 > mt.hi)) hits.push_back(j * n_all + t->n_tests + m);
+          }
+          continue;
+        }
         if (out[j].etype != SW_EV_LOCATION) continue;
         const double x = out[j].v0, y = out[j].v1;
         for (int32_t k = 0; k < t->n_tests; ++k) {
@@ -767,23 +782,24 @@ int32_t swce_process(void* p, const SwCeTables* t, SwCeStep* st, const SwEventRe
           const bool out_band = y < t->zone_bbox[4 * z + 1] || y > t->zone_bbox[4 * z + 3];
           const bool inside = !out_band &&
                               pip(t->zone_vtx + 2 * (int64_t)t->zone_off[z], t->zone_off[z + 1] - t->zone_off[z], x, y);
-          if ((zt.condition == 0) == inside) hits.push_back(j * t->n_tests + k);
+          if ((zt.condition == 0) == inside) hits.push_back(j * n_all + k);
         }
       }
     });
     for (int w = 0; w < T && (int64_t)gen.size() < t->gen_cap; ++w)
       for (int64_t hk : e->scratch64[w]) {
         if ((int64_t)gen.size() >= t->gen_cap) break;
-        const int64_t j = hk / t->n_tests;
-        const int32_t k = (int32_t)(hk % t->n_tests);
+        const int64_t j = hk / n_all;
+        const int32_t k = (int32_t)(hk % n_all);
+        const bool zone = k < t->n_tests;
         SwEventRec g;
         memset(&g, 0, sizeof(g));
         g.event_date = now_ms;
-        g.name_hash = t->test_hash[k];
+        g.name_hash = zone ? t->test_hash[k] : t->mtest_hash[k - t->n_tests];
         g.aux_off = (uint32_t)k;
         g.etype = SW_EV_ALERT;
         g.src_rank = (uint8_t)t->rank;
-        g.level = (uint8_t)t->tests[k].level;
+        g.level = (uint8_t)(zone ? t->tests[k].level : t->mtest_level[k - t->n_tests]);
         gen.push_back(g);
         gen_asg.push_back(out[j].assignment);
       }

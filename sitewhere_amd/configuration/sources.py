@@ -185,9 +185,11 @@ class InboundProcessingProvider(ModelProvider):
 
     def initialize_roles(self):
         self.role(Role("inbound-processing", "Inbound Processing", permanent=True,
-                       children=("engine-capacity", "gpu-zone-tests", "engine-checkpoint")))
+                       children=("engine-capacity", "gpu-zone-tests", "gpu-measurement-tests",
+                                 "engine-checkpoint")))
         self.role(Role("engine-capacity", "Engine Capacity", key="capacity"))
         self.role(Role("gpu-zone-tests", "Zone Tests", key="zoneTests", multiple=True))
+        self.role(Role("gpu-measurement-tests", "Measurement Tests", key="measurementTests", multiple=True))
         self.role(Role("engine-checkpoint", "Checkpoint", key="checkpoint"))
 
     def initialize_elements(self):
@@ -247,6 +249,14 @@ class InboundProcessingProvider(ModelProvider):
             Attr("alertType", "String", "alert type", default="zone.alert"),
             Attr("alertLevel", "Integer", "0 Info .. 3 Critical", default=1),
             Attr("alertMessage", "String", "alert message")], icon="map"))
+        self.element(Element("Measurement Test", "gpu-measurement-tests", (),
+                             "Threshold on a measurement's value, evaluated inside the engine step.", [
+            Attr("measurement", "String", "measurement name", required=True),
+            Attr("min", "Decimal", "alert when the value is below (strict)"),
+            Attr("max", "Decimal", "alert when the value is above (strict)"),
+            Attr("alertType", "String", "alert type (default: <measurement>.threshold)"),
+            Attr("alertLevel", "Integer", "0 Info .. 3 Critical", default=1),
+            Attr("alertMessage", "String", "alert message")], icon="show_chart"))
         self.element(Element("Checkpoint", "engine-checkpoint", (),
                              "Engine-shard snapshots; raw offsets commit only when covered.", [
                                  Attr("path", "String", "safetensors file (supports [[tenant.token]])", required=True,

@@ -112,6 +112,7 @@ ASG_STATE = np.dtype([("last", "<u8"), ("missing", "<u8"), ("loc_date", "<u8"), 
 MS_SLOT = np.dtype([("key", "<u8"), ("date", "<u8"), ("eid1", "<u8"), ("pad", "<u8")])
 
 ZONE_TEST = np.dtype([("zone", "<i4"), ("condition", "<i4"), ("alert_name_id", "<i4"), ("level", "<i4")])
+MX_TEST = np.dtype([("name_hash", "<u8"), ("lo", "<f8"), ("hi", "<f8")])     # SwMxTest
 
 # Stats slots (SW_STAT_* in swengine.h).
 N_STATS = 24            # SW_N_STATS (csrc/include/swengine.h): slots of the stats arrays

@@ -71,6 +71,8 @@ FIELDS = [
     # lossless re-key: per-input string bytes, per-tile byte matrix, cut metadata, carry string heaps
     ("part_len", P), ("part_bytes", P), ("part_meta", P), ("carry_spans", P), ("carry_str", P),
     ("spill_spans", P), ("spill_str", P), ("n_spill_str", P), ("carry_str_cap", I),
+    # rules (measurement tests): packed SwMxTest table, test indices n_tests .. n_tests + n_mtests - 1
+    ("mtests", P), ("n_mtests", I),
 ]
 
 

@@ -51,6 +51,8 @@ def save_engine(engine, path: str, include_store: bool = False, extra: dict | No
             "zones": [[z.token, [list(map(float, v)) for v in z.vertices]] for z in engine.zones],
             "tests": [[t.zone_token, t.condition, t.alert_type, int(t.alert_level), t.alert_message]
                       for t in engine.tests],
+            "mtests": [[t.measurement, t.min, t.max, t.alert_type, int(t.alert_level), t.alert_message]
+                       for t in engine.mtests],
             "extra": extra or {},
         }
     tmp = f"{path}.tmp-{os.getpid()}"
@@ -70,7 +72,7 @@ def load_engine(engine, path: str) -> dict:
     kind and sizing.  Returns the metadata ``extra`` dict the writer attached."""
     from safetensors.numpy import load_file
 
-    from .engine_base import Zone, ZoneTest
+    from .engine_base import MeasurementTest, Zone, ZoneTest
 
     meta = read_meta(path)
     if meta.get("format") != FORMAT:
@@ -91,7 +93,10 @@ def load_engine(engine, path: str) -> dict:
         engine.names = {int(h): s for h, s in meta["names"].items()}
         zones = [Zone(tok, [tuple(v) for v in verts]) for tok, verts in meta["zones"]]
         tests = [ZoneTest(*t) for t in meta["tests"]]
+        engine.set_measurement_rules([])
         engine.set_zone_rules(zones, tests)
+        # a checkpoint from before measurement tests existed has none
+        engine.set_measurement_rules([MeasurementTest(*t) for t in meta.get("mtests", [])])
         engine.restore_state({k[4:]: v for k, v in arrays.items() if k.startswith("eng/")},
                              bool(meta["include_store"]))
     return meta.get("extra", {})

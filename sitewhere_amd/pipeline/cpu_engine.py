@@ -504,22 +504,34 @@ class CpuInboundEngine(EngineBase):
             self.ff.add_persisted(work[ok]["alt_hash"])
         self._state(work[ok], asg[ok], now_ms)
         self.cursor += len(ok)
-        # rules on persisted locations
+        # rules on persisted rows: zone tests on locations, measurement tests on measurements
         gen, gen_dev, gen_asg = [], [], []
-        if self.tests:
+        if self.tests or self.mtests:
             vtx, zoff, _, tests, hashes = self.zone_arrays()
             polys = [vtx.reshape(-1, 2)[zoff[z]:zoff[z + 1]] for z in range(len(zoff) - 1)]
-            for o in out_rows:
+            mtab, mlevels, mhashes = self.measurement_arrays()
+            nz = len(tests)
+
+            def fire(o, t, h, level):
+                if len(gen) < self.cfg.gen_cap:
+                    gen.append((0, 0, now_ms, int(h), 0.0, 0.0, 0.0, 0, t, 0, 0, 0, EV_ALERT, 0, self.rank, int(level)))
+                    gen_dev.append(int(self.asg_device[o[3]]))
+                    gen_asg.append(o[3])
+
+            for j, o in enumerate(out_rows):
+                if o[5] == EV_MEASUREMENT:
+                    # measurement tests (test indices nz ..): strict fp64 compares, NaN never fires
+                    name, v = int(work[ok[j]]["name_hash"]), float(work[ok[j]]["v0"])
+                    for m, mt in enumerate(mtab):
+                        if int(mt["name_hash"]) == name and (v < float(mt["lo"]) or v > float(mt["hi"])):
+                            fire(o, nz + m, mhashes[m], mlevels[m])
+                    continue
                 if o[5] != EV_LOCATION:
                     continue
                 for t, zt in enumerate(tests):
                     inside = pip(polys[int(zt["zone"])], o[1], o[2])
                     if (int(zt["condition"]) == 0) == inside:
-                        if len(gen) < self.cfg.gen_cap:
-                            gen.append((0, 0, now_ms, int(hashes[t]), 0.0, 0.0, 0.0, 0, t, 0, 0, 0, EV_ALERT, 0,
-                                        self.rank, int(zt["level"])))
-                            gen_dev.append(int(self.asg_device[o[3]]))
-                            gen_asg.append(o[3])
+                        fire(o, t, hashes[t], zt["level"])
         n_rule = len(gen)
         do_presence = self.presence_due(now_ms) if presence is None else presence
         if do_presence and self.cfg.presence_missing_ms > 0:

@@ -46,6 +46,35 @@ class ZoneTest:
 
 
 @dataclass
+class MeasurementTest:
+    """Threshold rule on a measurement's value, evaluated inside the engine step (an addition: the
+    reference engine has zone tests only).  Fires when the value is below ``min`` or above ``max``
+    (strict, fp64); an absent bound never fires."""
+    measurement: str
+    min: float | None = None
+    max: float | None = None
+    alert_type: str = ""            # "" = f"{measurement}.threshold"
+    alert_level: int = 1
+    alert_message: str = ""         # "" = f"{measurement} outside [{min}, {max}]" (constant per rule)
+
+    def __post_init__(self):
+        if self.min is None and self.max is None:
+            raise ValueError(f"measurement test on {self.measurement!r} has neither min nor max")
+        for b in (self.min, self.max):
+            if b is not None and b != b:
+                raise ValueError(f"measurement test on {self.measurement!r} has a NaN bound")
+        if self.min is not None and self.max is not None and self.min > self.max:
+            raise ValueError(f"measurement test on {self.measurement!r}: min {self.min} > max {self.max}")
+        if not self.alert_type:
+            self.alert_type = f"{self.measurement}.threshold"
+        if not self.alert_message:
+            self.alert_message = f"{self.measurement} outside [{self.min}, {self.max}]"
+
+
+MAX_RULE_TESTS = 64     # one fired bit per test in a row's 64-bit mask (ZONE_LDS_TESTS in swgpu.hip)
+
+
+@dataclass
 class StepResult:
     """What one micro-batch produced (host copies; filled by ``finalize``)."""
     n_msgs: int = 0
@@ -112,6 +141,7 @@ class EngineBase:
         # zones
         self.zones: list[Zone] = []
         self.tests: list[ZoneTest] = []
+        self.mtests: list[MeasurementTest] = []
         self.batch_seq = 0
         self.presence_enabled = True
         self._last_presence_check = None
@@ -198,6 +228,9 @@ class EngineBase:
     # ------------------------------------------------------------------ zones / rules
     def set_zone_rules(self, zones: list[Zone], tests: list[ZoneTest]):
         with self._lock:
+            if len(tests) + len(self.mtests) > MAX_RULE_TESTS:
+                raise ValueError(f"{len(tests)} zone tests + {len(self.mtests)} measurement tests exceed "
+                                 f"{MAX_RULE_TESTS}")
             self.zones = list(zones)
             self.tests = list(tests)
             for t in tests:
@@ -206,6 +239,44 @@ class EngineBase:
 
     def _zones_changed(self):
         pass
+
+    def set_measurement_rules(self, tests: list[MeasurementTest]):
+        """Replace the measurement (threshold) tests; takes effect from the next step."""
+        tests = list(tests)
+        for t in tests:
+            t.__post_init__()                 # a rule edited after construction is validated too
+        with self._lock:
+            if len(self.tests) + len(tests) > MAX_RULE_TESTS:
+                raise ValueError(f"{len(self.tests)} zone tests + {len(tests)} measurement tests exceed "
+                                 f"{MAX_RULE_TESTS}")
+            self.mtests = tests
+            for t in tests:
+                self.names[hash64(t.alert_type)] = t.alert_type
+            self._rules_changed()
+
+    def _rules_changed(self):
+        """Hook: engines refresh their packed measurement-rule tables."""
+
+    @property
+    def rule_tests(self) -> list:
+        """Every rule in test-index order: zone tests, then measurement tests (a generated alert's
+        ``aux_off`` indexes this list)."""
+        return list(self.tests) + list(self.mtests)
+
+    def measurement_arrays(self):
+        """Packed measurement tests: table MX_TEST[M] (name_hash u64, lo f64, hi f64; an absent bound
+        is -inf / +inf), levels i32[M], alert-type hashes u64[M]."""
+        from ..models.columnar import MX_TEST
+
+        tab = np.zeros(len(self.mtests), MX_TEST)
+        levels = np.zeros(len(self.mtests), np.int32)
+        hashes = np.zeros(len(self.mtests), np.uint64)
+        for i, t in enumerate(self.mtests):
+            tab[i] = (hash64(t.measurement), -np.inf if t.min is None else float(t.min),
+                      np.inf if t.max is None else float(t.max))
+            levels[i] = int(t.alert_level)
+            hashes[i] = hash64(t.alert_type)
+        return tab, levels, hashes
 
     def zone_arrays(self):
         """Flattened zone polygons: vtx [2*V] f64, off [Z+1] i32, bbox [4*Z] f64, tests ZONE_TEST[T]."""

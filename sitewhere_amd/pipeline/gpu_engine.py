@@ -379,10 +379,18 @@ class GpuInboundEngine(EngineBase):
         self.t["zone_vtx"] = torch.from_numpy(vtx).to(d)
         self.t["zone_off"] = torch.from_numpy(off).to(d)
         self.t["zone_bbox"] = torch.from_numpy(bbox).to(d)
-        self.t["tests"] = torch.from_numpy(tests.view(np.uint8).copy() if len(tests) else np.zeros(16, np.uint8)).to(d)
-        self.t["test_hash"] = torch.from_numpy(hashes.view(np.int64).copy() if len(hashes) else np.zeros(1, np.int64)).to(d)
         self._n_zones, self._n_tests = len(off) - 1, len(tests)
         self._n_zone_vtx = int(off[-1]) if len(off) else 0
+        # measurement tests: their level / alert-type entries follow the zone tests' (one test-index
+        # space, k_zone_emit reads both by index); the packed bounds table is k_mx_mask's
+        mtab, mlevels, mhashes = self.measurement_arrays()
+        mrows = np.zeros(len(mtab), tests.dtype)
+        mrows["zone"], mrows["alert_name_id"], mrows["level"] = -1, -1, mlevels
+        tests, hashes = np.concatenate([tests, mrows]), np.concatenate([hashes, mhashes])
+        self.t["tests"] = torch.from_numpy(tests.view(np.uint8).copy() if len(tests) else np.zeros(16, np.uint8)).to(d)
+        self.t["test_hash"] = torch.from_numpy(hashes.view(np.int64).copy() if len(hashes) else np.zeros(1, np.int64)).to(d)
+        self.t["mtests"] = torch.from_numpy(mtab.view(np.uint8).copy() if len(mtab) else np.zeros(24, np.uint8)).to(d)
+        self._n_mtests = len(mtab)
 
     def _apply_zone_ptrs(self):
         a = self.args
@@ -390,6 +398,10 @@ class GpuInboundEngine(EngineBase):
         a.n_zones, a.tests, a.n_tests = self._n_zones, _ptr(self.t["tests"]), self._n_tests
         a.n_zone_vtx = self._n_zone_vtx
         a.test_name_hash = _ptr(self.t["test_hash"])
+        a.mtests, a.n_mtests = _ptr(self.t["mtests"]), self._n_mtests
+
+    def _rules_changed(self):
+        self._zones_changed()
 
     def _zones_changed(self):
         if hasattr(self, "args"):

@@ -41,7 +41,8 @@ class _Tables(ctypes.Structure):
         [("n_tests", ctypes.c_int32), ("rank", ctypes.c_int32), ("world", ctypes.c_int32),
          ("batch_seq", ctypes.c_int32), ("gen_cap", ctypes.c_int64), ("presence_hash", ctypes.c_uint64),
          ("presence_missing_ms", ctypes.c_int64), ("stats", _P), ("cluster", ctypes.c_int32),
-         ("pad0", ctypes.c_int32)]
+         ("pad0", ctypes.c_int32), ("mtests", _P), ("mtest_level", _P), ("mtest_hash", _P),
+         ("n_mtests", ctypes.c_int64)]
 
 
 class _Step(ctypes.Structure):
@@ -99,6 +100,7 @@ class NativeCpuEngine(CpuInboundEngine):
         self._out_pool: dict = {}       # recycled outbound buffers per dtype (see _out_buffer)
         self._status = np.zeros(cfg.rec_cap, np.uint8)
         self._zones = None
+        self._mx = None
         self._zones_changed()
         self._dec, self._dec_k = [None, None], 0
         self._dsp = [None, None]
@@ -156,6 +158,9 @@ class NativeCpuEngine(CpuInboundEngine):
     def _zones_changed(self):
         self._zones = self.zone_arrays() if self.tests else None
 
+    def _rules_changed(self):
+        self._mx = self.measurement_arrays() if self.mtests else None
+
     # ------------------------------------------------------------------ phases
     def decode_phase(self, raw, offs, now_ms):
         # two decode buffers, alternating: a batch's records stay valid while the next one decodes
@@ -184,6 +189,9 @@ class NativeCpuEngine(CpuInboundEngine):
             self._zone_keep = (vtx, zoff, bbox, tests, hashes)
             t.zone_vtx, t.zone_off, t.zone_bbox = _ptr(vtx), _ptr(zoff), _ptr(bbox)
             t.tests, t.test_hash, t.n_tests = _ptr(tests), _ptr(hashes), len(tests)
+        if self._mx is not None:
+            mtab, mlevels, mhashes = self._mx_keep = self._mx
+            t.mtests, t.mtest_level, t.mtest_hash, t.n_mtests = _ptr(mtab), _ptr(mlevels), _ptr(mhashes), len(mtab)
         t.rank, t.world, t.batch_seq = self.rank, self.world, self.batch_seq
         t.gen_cap = self.cfg.gen_cap
         t.presence_hash = self.presence_hash

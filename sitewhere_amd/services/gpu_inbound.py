@@ -34,7 +34,7 @@ from ..persistence.columnar import encode_batch, frame_batch
 from ..models.domain import (AlertLevel, AlertSource, DeviceAlert, DeviceAssignmentStatus, DeviceLocation,
                              DeviceMeasurement, DeviceStateChange, now_ms)
 from ..pipeline.config import EngineConfig
-from ..pipeline.engine_base import Zone, ZoneTest
+from ..pipeline.engine_base import MeasurementTest, Zone, ZoneTest
 from ..pipeline.bus_io import MultiRawBatch, RawBatch, parse_raw_batch
 from ..pipeline.fleet import fingerprint_str, pack_messages
 from ..rpc import codec
@@ -120,6 +120,14 @@ class GpuInboundTenantEngine(InboundProcessingTenantEngine):
         self.zone_tests = [ZoneTest(z["zoneToken"], z.get("condition", "inside"), z.get("alertType", "zone.alert"),
                                     int(z.get("alertLevel", 1)), z.get("alertMessage", ""))
                            for z in cfg.get("zoneTests", [])]
+        # threshold rules evaluated inside the engine step (an addition: configure a rule here or in
+        # rule-processing, not both, or it alerts twice)
+        self.measurement_tests = [MeasurementTest(m["measurement"],
+                                                  None if m.get("min") is None else float(m["min"]),
+                                                  None if m.get("max") is None else float(m["max"]),
+                                                  m.get("alertType", ""), int(m.get("alertLevel", 1)),
+                                                  m.get("alertMessage", ""))
+                                  for m in cfg.get("measurementTests", [])]
         # checkpoint / resume: {"path": ..., "everyBatches": N, "includeStore": false}.
         # With a checkpoint the raw consumer commits only the offsets a snapshot on disk covers.
         ck = cfg.get("checkpoint") or {}
@@ -272,6 +280,13 @@ class GpuInboundTenantEngine(InboundProcessingTenantEngine):
                     self._asg_entities[i] = a
                     self._asg_dirty.add(i)
         self._load_zones()
+        self._load_measurement_rules()
+
+    def _load_measurement_rules(self):
+        """The configured measurement tests replace whatever the engine holds (a restored checkpoint's
+        included)."""
+        if self.measurement_tests or self.engine.mtests:
+            self.engine.set_measurement_rules(self.measurement_tests)
 
     def _load_zones(self):
         if not self.zone_tests:
@@ -919,7 +934,7 @@ class GpuInboundTenantEngine(InboundProcessingTenantEngine):
                 self._reload_names()
             names = dict(self._nid2name) if len(self._nid2name) != self._names_sent else {}
             self._names_sent = len(self._nid2name)
-        rules = {t.alert_type: t.alert_message for t in self.engine.tests}
+        rules = {t.alert_type: t.alert_message for t in self.engine.rule_tests}
         self._ctx_delta = ctx
         return asg, names, rules
 
@@ -1065,7 +1080,7 @@ class GpuInboundTenantEngine(InboundProcessingTenantEngine):
         if getattr(res, "block", None) is not None:
             return self._block_events(res)
         eids = res.event_ids()
-        tests = self.engine.tests
+        tests = self.engine.rule_tests
         events = []
         for r, eid in zip(out, eids):
             a = self._asg_entities.get(int(r["assignment"]))
@@ -1106,7 +1121,7 @@ class GpuInboundTenantEngine(InboundProcessingTenantEngine):
             if a is not None:
                 asg[int(ai)] = [a.id, a.device_id, a.customer_id, a.area_id, a.asset_id]
         names = {int(n): self._name(int(n)) for n in np.unique(cols["name"]).tolist() if int(n) != NO_NAME}
-        rules = {t.alert_type: t.alert_message for t in self.engine.tests}
+        rules = {t.alert_type: t.alert_message for t in self.engine.rule_tests}
         return [materialize_row(cols, i, asg, names, rules) for i in range(len(cols["etype"]))
                 if int(cols["asg"][i]) in asg]
 
@@ -1299,7 +1314,7 @@ class GpuInboundApi:
         total, cols, eids = e.engine.query_store(self._ETYPE[event_type], asg, start_date, end_date, page_number,
                                                  page_size)
         out = []
-        rules = {t.alert_type: t.alert_message for t in e.engine.tests}
+        rules = {t.alert_type: t.alert_message for t in e.engine.rule_tests}
         for i in range(len(eids)):
             a = e._asg_entities.get(int(cols["asg"][i]))
             if a is None:
