@@ -28,6 +28,7 @@
 #include "swdecode.h"
 #include "swengine.h"
 #include "swseg.h"
+#include "swblock.h"
 
 #define BLK 256
 #define WAVES (BLK / 64)
@@ -36,8 +37,6 @@
 #define MAX_GRID 2048
 #define STAGE_BYTES (32 * 1024)
 #define MAX_PROBE 4096  // open-addressing probe bound (tables are sized for load <= 0.5)
-
-typedef unsigned long long ull;
 
 // Workgroup id as the kernels see it.  The dispatcher deals workgroups round-robin over the 8 XCDs
 // (each with its own L2); with SW_XCD_REMAP the ids are permuted (bijectively, any grid size) so the
@@ -64,156 +63,12 @@ static inline int grid_for(int64_t n) {
   return (int)g;
 }
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ ull lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
-// Block-wide exclusive scan of one value per thread; returns the prefix and the block total.
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total, uint32_t* lds) {
-  const uint32_t lane = lane_id(), wid = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t t = __shfl_up(inc, d, 64);
-    if (lane >= (uint32_t)d) inc += t;
-  }
-  if (lane == 63) lds[wid] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t acc = 0;
-    for (int w = 0; w < WAVES; ++w) { uint32_t t = lds[w]; lds[w] = acc; acc += t; }
-    lds[WAVES] = acc;
-  }
-  __syncthreads();
-  uint32_t res = inc - v + lds[wid];
-  *total = lds[WAVES];
-  __syncthreads();
-  return res;
-}
-
-// Sum of v[0 .. k), returned to every thread of the block: the prologue reduce of the per-tile sums
-// the PREVIOUS kernel wrote, in place of a separate single-workgroup scan dispatch between the two
-// (a few thousand L2-resident u32s: ~1-2 us of loads per block against ~5-8 us per extra dispatch,
-// and no flags, fences or counters -- the kernel boundary is the only synchronisation).
-__device__ __forceinline__ uint32_t block_sum_prefix(const uint32_t* v, int64_t k, uint32_t* lds) {
-  uint32_t s = 0;
-  for (int64_t i = threadIdx.x; i < k; i += BLK) s += v[i];
-  uint32_t tot;
-  block_excl_scan(s, &tot, lds);
-  return tot;
-}
-
 // ============================================================================ scan
-// Exclusive scan of u32[n] -> out, total -> *total.  n <= TILE * (BLK * 64).
-__global__ void k_scan_tiles(const uint32_t* __restrict__ in, int64_t n, uint32_t* __restrict__ tsum) {
-  __shared__ uint32_t lds[WAVES + 1];
-  const int64_t base = (int64_t)BID * TILE;
-  uint32_t s = 0;
-#pragma unroll
-  for (int k = 0; k < TILE_ITEMS; ++k) {
-    int64_t i = base + (int64_t)k * BLK + threadIdx.x;
-    if (i < n) s += in[i];
-  }
-  uint32_t tot;
-  block_excl_scan(s, &tot, lds);
-  if (threadIdx.x == 0) tsum[BID] = tot;
-}
-
-__global__ void k_scan_apply(const uint32_t* __restrict__ in, int64_t n, const uint32_t* __restrict__ tsum,
-                             uint32_t* __restrict__ out) {
-  __shared__ uint32_t lds[WAVES + 1];
-  const int64_t base = (int64_t)BID * TILE;
-  uint32_t run = tsum[BID];
-#pragma unroll
-  for (int k = 0; k < TILE_ITEMS; ++k) {
-    int64_t i = base + (int64_t)k * BLK + threadIdx.x;
-    uint32_t v = i < n ? in[i] : 0;
-    uint32_t tot;
-    uint32_t pre = block_excl_scan(v, &tot, lds);
-    if (i < n) out[i] = run + pre;
-    run += tot;
-  }
-}
-
-// Single-pass exclusive scan (decoupled look-back): one dispatch instead of tiles + sums + apply.
-// Workgroups take tiles in ticket order, publish their tile aggregate, then walk back over their
-// predecessors' 64-bit state words (flag in the top bits) until an inclusive prefix.  The
-// workgroup that finishes last zeroes the state (ticket, done counter, tile words), so the next
-// launch -- including a hipGraph replay with the same arguments -- starts clean: no memset node.
-// state = u64[2 + nt]: [0] ticket, [1] done, [2..] tile words.
-#define SLB_AGG (1ull << 62)
-#define SLB_INC (2ull << 62)
-#define SLB_VAL ((1ull << 62) - 1)
-#define SLB_SPIN_LIMIT (1u << 26)
-
-__device__ __forceinline__ ull slb_load(const ull* p) {
-  return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void slb_store(ull* p, ull v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__global__ void k_scan_lb(const uint32_t* __restrict__ in, int64_t n, uint32_t* __restrict__ out,
-                          uint32_t* __restrict__ total, ull* __restrict__ state, int64_t nt) {
-  __shared__ uint32_t lds[WAVES + 1];
-  __shared__ uint32_t s_tile;
-  __shared__ ull s_excl;
-  if (threadIdx.x == 0) s_tile = (uint32_t)atomicAdd(&state[0], 1ull);
-  __syncthreads();
-  const int64_t tile = s_tile;
-  const int64_t base = tile * TILE + (int64_t)threadIdx.x * TILE_ITEMS;
-  uint32_t v[TILE_ITEMS];
-  uint32_t sum = 0;
-#pragma unroll
-  for (int k = 0; k < TILE_ITEMS; ++k) {
-    const int64_t i = base + k;
-    v[k] = i < n ? in[i] : 0u;
-    sum += v[k];
-  }
-  uint32_t agg;
-  const uint32_t pre = block_excl_scan(sum, &agg, lds);
-  if (threadIdx.x == 0) {
-    ull excl = 0;
-    ull* tw = state + 2;
-    if (tile == 0) {
-      slb_store(&tw[0], SLB_INC | agg);
-    } else {
-      slb_store(&tw[tile], SLB_AGG | agg);
-      for (int64_t p = tile - 1; p >= 0;) {
-        ull w = slb_load(&tw[p]);
-        uint32_t spins = 0;
-        while ((w >> 62) == 0 && ++spins < SLB_SPIN_LIMIT) {
-          __builtin_amdgcn_s_sleep(1);
-          w = slb_load(&tw[p]);
-        }
-        excl += w & SLB_VAL;
-        if ((w >> 62) == 2) break;
-        --p;
-      }
-      slb_store(&tw[tile], SLB_INC | (excl + agg));
-    }
-    s_excl = excl;
-    if (tile == nt - 1 && total) *total = (uint32_t)(excl + agg);
-  }
-  __syncthreads();
-  uint32_t run = (uint32_t)s_excl + pre;
-#pragma unroll
-  for (int k = 0; k < TILE_ITEMS; ++k) {
-    const int64_t i = base + k;
-    if (i < n) out[i] = run;
-    run += v[k];
-  }
-  __syncthreads();
-  // the last workgroup to finish resets the state for the next launch (nobody reads it any more)
-  if (threadIdx.x == 0) s_tile = (uint32_t)(atomicAdd(&state[1], 1ull) == (ull)(nt - 1));
-  __syncthreads();
-  if (s_tile) {
-    for (int64_t i = threadIdx.x; i < nt + 2; i += BLK) state[i] = 0;
-  }
-}
-
-// One-workgroup exclusive scan for short arrays (tile counters: a few thousand entries): each thread
-// scans a contiguous run.  Cheaper than any multi-workgroup scheme at this size -- the look-back
-// below pays cross-XCD flag latency even for 2 tiles (10-15 us measured against ~5 us here).
+// Exclusive scan of u32[n] -> out, total -> *total (when non-null).
+// One-workgroup scan for short arrays (tile counters: a few thousand entries): each thread scans a
+// contiguous run.  Cheaper than any multi-workgroup scheme at this size (~5 us).
 __global__ void k_scan_block(const uint32_t* __restrict__ in, int64_t n, uint32_t* __restrict__ out,
                              uint32_t* __restrict__ total) {
   __shared__ uint32_t lds[WAVES + 1];
@@ -230,16 +85,50 @@ __global__ void k_scan_block(const uint32_t* __restrict__ in, int64_t n, uint32_
 }
 #define SCAN_BLOCK_MAX (BLK * 64)
 
+// Longer arrays, reduce-then-scan in two dispatches: each tile's sum, then every tile reduces the
+// sums before it in its prologue and scans itself.  tsum is fully rewritten: no state to arm.
+__global__ void k_scan_tiles(const uint32_t* __restrict__ in, int64_t n, uint32_t* __restrict__ tsum) {
+  __shared__ uint32_t lds[WAVES + 1];
+  const int64_t base = (int64_t)BID * TILE;
+  uint32_t s = 0;
+#pragma unroll
+  for (int k = 0; k < TILE_ITEMS; ++k) {
+    int64_t i = base + (int64_t)k * BLK + threadIdx.x;
+    if (i < n) s += in[i];
+  }
+  uint32_t tot;
+  block_excl_scan(s, &tot, lds);
+  if (threadIdx.x == 0) tsum[BID] = tot;
+}
+
+__global__ void k_scan_apply(const uint32_t* __restrict__ in, int64_t n, const uint32_t* __restrict__ tsum,
+                             uint32_t* __restrict__ out, uint32_t* __restrict__ total) {
+  __shared__ uint32_t lds[WAVES + 1];
+  const int64_t base = (int64_t)BID * TILE;
+  uint32_t run = block_sum_prefix(tsum, BID, lds);
+  if (BID == gridDim.x - 1 && threadIdx.x == 0 && total) *total = run + tsum[BID];
+#pragma unroll
+  for (int k = 0; k < TILE_ITEMS; ++k) {
+    int64_t i = base + (int64_t)k * BLK + threadIdx.x;
+    uint32_t v = i < n ? in[i] : 0;
+    uint32_t tot;
+    uint32_t pre = block_excl_scan(v, &tot, lds);
+    if (i < n) out[i] = run + pre;
+    run += tot;
+  }
+}
+
+// tmp holds one u32 per tile above SCAN_BLOCK_MAX (any contents, any alignment).
 static int launch_scan(const uint32_t* in, int64_t n, uint32_t* out, uint32_t* total, uint32_t* tmp,
                        int64_t tmp_len, hipStream_t s) {
   if (n <= SCAN_BLOCK_MAX) {
     k_scan_block<<<1, BLK, 0, s>>>(in, n, out, total);
     return 0;
   }
-  int64_t nt = (n + TILE - 1) / TILE;
-  if (nt < 1) nt = 1;
-  if (2 * (nt + 2) > tmp_len || ((uintptr_t)tmp & 7)) return -2;     // tmp holds u64[2 + nt]
-  k_scan_lb<<<(unsigned)nt, BLK, 0, s>>>(in, n, out, total, reinterpret_cast<ull*>(tmp), nt);
+  const int64_t nt = (n + TILE - 1) / TILE;
+  if (nt > tmp_len) return -2;
+  k_scan_tiles<<<(unsigned)nt, BLK, 0, s>>>(in, n, tmp);
+  k_scan_apply<<<(unsigned)nt, BLK, 0, s>>>(in, n, tmp, out, total);
   return 0;
 }
 
@@ -474,29 +363,6 @@ __device__ __forceinline__ uint32_t part_str_len(const SwEngineArgs& a, const Sw
 #define PM_KEPT 192              // spilled records kept in the next carry
 #define PM_KEPT_BYTES 193        // their string bytes (the next carry heap's size)
 
-// Block-wide exclusive scan of one u64 per thread (string byte prefixes can pass 2^32).
-__device__ __forceinline__ ull block_excl_scan64(ull v, ull* total, ull* lds) {
-  const uint32_t lane = lane_id(), wid = threadIdx.x >> 6;
-  ull inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const ull t = __shfl_up(inc, d, 64);
-    if (lane >= (uint32_t)d) inc += t;
-  }
-  if (lane == 63) lds[wid] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ull acc = 0;
-    for (int w = 0; w < WAVES; ++w) { const ull t = lds[w]; lds[w] = acc; acc += t; }
-    lds[WAVES] = acc;
-  }
-  __syncthreads();
-  const ull res = inc - v + lds[wid];
-  *total = lds[WAVES];
-  __syncthreads();
-  return res;
-}
-
 // Per tile: records and string bytes per destination ([world][ntiles] each), the destination of
 // every input (part_owner) and its exchange bytes (part_len; a record whose strings alone exceed a
 // whole slab goes without them, counted in str_drops[0]).
@@ -566,7 +432,7 @@ __global__ __launch_bounds__(BLK) void k_part_cut(const uint32_t* __restrict__ t
     const int64_t t = c0 + threadIdx.x;
     const ull v = t < ntiles ? tb[t] : 0ull;
     ull tot;
-    const ull ex = block_excl_scan64(v, &tot, red);
+    const ull ex = block_excl_scan(v, &tot, red);
     if (t < ntiles) bo[t] = acc + ex;
     acc += tot;
   }
@@ -596,8 +462,8 @@ __global__ __launch_bounds__(BLK) void k_part_cut(const uint32_t* __restrict__ t
       const bool mine = i < n && a.part_owner[i] == (uint8_t)q;
       const ull L = mine && strings ? (ull)(a.part_len[i] & ~PART_STRIP) : 0ull;
       ull totc, totb;
-      const ull exc = block_excl_scan64(mine ? 1ull : 0ull, &totc, red);
-      const ull exb = block_excl_scan64(L, &totb, red);
+      const ull exc = block_excl_scan(mine ? 1ull : 0ull, &totc, red);
+      const ull exb = block_excl_scan(L, &totb, red);
       if (mine && rc + exc + 1 <= (ull)a.shuf_cap && rb + exb + L <= blim) {
         atomicAdd(&fit_c, 1u);
         atomicAdd(&fit_b, L);
@@ -714,13 +580,7 @@ __global__ __launch_bounds__(BLK) void k_part_write(const SwEventRec* __restrict
       const bool mine = valid && o == q;
       const ull m = __ballot(mine);
       ull inc = mine ? Lb : 0ull;
-      if (strings) {
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-          const ull t = __shfl_up(inc, d, 64);
-          if (lane >= (uint32_t)d) inc += t;
-        }
-      }
+      if (strings) inc = wave_incl_scan(inc);
       if (mine) { my_rank = __popcll(m & lanemask_lt()); my_b = inc - Lb; }
       if (lane == 63) { wcnt[wid][q] = __popcll(m); wbyt[wid][q] = inc; }
       rem &= ~m;
@@ -2103,12 +1963,53 @@ __global__ void k_cl_prep(const uint32_t* __restrict__ ok_idx, const uint32_t* _
   }
 }
 
-int sw_radix_sort_u32(uint32_t* keys, uint32_t* vals, const uint32_t* n_ptr, int64_t cap, int bits, uint32_t* hist,
-                      uint32_t* vals_final, hipStream_t s);
-
+// The persisted rows' ids into the live generation of the store-backed filter, right behind
+// k_persist: 4 lanes per id, lane q loading 16-byte word q of the id's 64-byte bucket (one full-line
+// load per id instead of four 16-byte loads by one thread), a hit anywhere ends the id, else the lowest
+// lane holding a free slot claims it with one CAS (another id winning the slot: the group looks
+// again); a full bucket sends the id on to the next.  The bucket rule of ff_add.
 __global__ __launch_bounds__(BLK) void k_ff_add_rows(SwEngineArgs a, const SwEventRec* __restrict__ R,
                                                      const uint32_t* __restrict__ idx,
-                                                     const uint32_t* __restrict__ n_ptr, uint32_t cap);
+                                                     const uint32_t* __restrict__ n_ptr, uint32_t cap) {
+  if (!a.dd_ff) return;
+  const uint32_t n = *n_ptr < cap ? *n_ptr : cap;
+  uint32_t* __restrict__ t = a.dd_ff;
+  const int gens = (int)a.dd_ff_gens, g = (int)a.dd_ff_meta[0];
+  const int64_t bmask = a.dd_ff_bmask;
+  const uint32_t lane = threadIdx.x & 63u, sub = lane & 3u, grp = lane >> 2;   // 16 ids per wave
+  const ull gmask = 0xfull << (4u * grp);
+  const int64_t g0 = ((int64_t)BID * BLK + threadIdx.x) >> 2;
+  const int64_t gstride = ((int64_t)gridDim.x * BLK) >> 2;
+  uint32_t dropped = 0;
+  for (int64_t base = g0 - grp; base < (int64_t)n; base += gstride) {
+    const int64_t j = base + grp;
+    ull h = 0ull;
+    if (j < (int64_t)n) h = R[idx ? idx[j] : (uint32_t)j].alt_hash;
+    const ull m = sw_ff_mix(h);
+    const uint32_t fp = sw_ff_fp(m);
+    int64_t b = (int64_t)sw_ff_bucket(m, bmask);
+    bool pending = h != 0ull;
+    for (int p = 0; p < 2 * SW_FF_MAX_PROBE && __any(pending); ++p) {
+      uint32_t* sl = t + (b * gens + g) * SW_FF_SLOTS;
+      uint4 v = make_uint4(1u, 1u, 1u, 1u);
+      if (pending) v = reinterpret_cast<const uint4*>(sl)[sub];
+      const bool hit = pending && (v.x == fp || v.y == fp || v.z == fp || v.w == fp);
+      if (__ballot(hit) & gmask) pending = false;
+      const bool zero = pending && (!v.x || !v.y || !v.z || !v.w);
+      const ull zb = __ballot(zero) & gmask;
+      bool ok = false;
+      if (pending && zb && lane == (uint32_t)(__ffsll((long long)zb) - 1)) {
+        const int k = !v.x ? 0 : !v.y ? 1 : !v.z ? 2 : 3;
+        const uint32_t old = atomicCAS(&sl[4u * sub + (uint32_t)k], 0u, fp);
+        ok = old == 0u || old == fp;
+      }
+      if (__ballot(ok) & gmask) pending = false;
+      else if (pending && !zb) b = (b + 1) & bmask;   // full without the id: the chain goes on
+    }
+    if (pending && sub == 0u) ++dropped;
+  }
+  if (dropped) atomicAdd((ull*)&a.dd_ff_meta[5], (ull)dropped);
+}
 
 // Phase D: validate, dedup, persist, enrich, state, rules, presence.
 int sw_phase_process(const SwEngineArgs* ap, uint32_t* scratch4, hipStream_t s) {
@@ -2180,54 +2081,6 @@ __global__ void k_set_step_params(SwStepParams* sp, int64_t now_ms, int64_t batc
 
 // Add ids to generation g of the store-backed dedup filter (warm start from the event store's
 // blocks, newest first; see EngineBase.filter_seed).
-// The persisted rows' ids into the live generation of the store-backed filter, right behind
-// k_persist: 4 lanes per id, lane q loading 16-byte word q of the id's 64-byte bucket (one full-line
-// load per id instead of four 16-byte loads by one thread), a hit anywhere ends the id, else the lowest
-// lane holding a free slot claims it with one CAS (another id winning the slot: the group looks
-// again); a full bucket sends the id on to the next.  The bucket rule of ff_add.
-__global__ __launch_bounds__(BLK) void k_ff_add_rows(SwEngineArgs a, const SwEventRec* __restrict__ R,
-                                                     const uint32_t* __restrict__ idx,
-                                                     const uint32_t* __restrict__ n_ptr, uint32_t cap) {
-  if (!a.dd_ff) return;
-  const uint32_t n = *n_ptr < cap ? *n_ptr : cap;
-  uint32_t* __restrict__ t = a.dd_ff;
-  const int gens = (int)a.dd_ff_gens, g = (int)a.dd_ff_meta[0];
-  const int64_t bmask = a.dd_ff_bmask;
-  const uint32_t lane = threadIdx.x & 63u, sub = lane & 3u, grp = lane >> 2;   // 16 ids per wave
-  const ull gmask = 0xfull << (4u * grp);
-  const int64_t g0 = ((int64_t)BID * BLK + threadIdx.x) >> 2;
-  const int64_t gstride = ((int64_t)gridDim.x * BLK) >> 2;
-  uint32_t dropped = 0;
-  for (int64_t base = g0 - grp; base < (int64_t)n; base += gstride) {
-    const int64_t j = base + grp;
-    ull h = 0ull;
-    if (j < (int64_t)n) h = R[idx ? idx[j] : (uint32_t)j].alt_hash;
-    const ull m = sw_ff_mix(h);
-    const uint32_t fp = sw_ff_fp(m);
-    int64_t b = (int64_t)sw_ff_bucket(m, bmask);
-    bool pending = h != 0ull;
-    for (int p = 0; p < 2 * SW_FF_MAX_PROBE && __any(pending); ++p) {
-      uint32_t* sl = t + (b * gens + g) * SW_FF_SLOTS;
-      uint4 v = make_uint4(1u, 1u, 1u, 1u);
-      if (pending) v = reinterpret_cast<const uint4*>(sl)[sub];
-      const bool hit = pending && (v.x == fp || v.y == fp || v.z == fp || v.w == fp);
-      if (__ballot(hit) & gmask) pending = false;
-      const bool zero = pending && (!v.x || !v.y || !v.z || !v.w);
-      const ull zb = __ballot(zero) & gmask;
-      bool ok = false;
-      if (pending && zb && lane == (uint32_t)(__ffsll((long long)zb) - 1)) {
-        const int k = !v.x ? 0 : !v.y ? 1 : !v.z ? 2 : 3;
-        const uint32_t old = atomicCAS(&sl[4u * sub + (uint32_t)k], 0u, fp);
-        ok = old == 0u || old == fp;
-      }
-      if (__ballot(ok) & gmask) pending = false;
-      else if (pending && !zb) b = (b + 1) & bmask;   // full without the id: the chain goes on
-    }
-    if (pending && sub == 0u) ++dropped;
-  }
-  if (dropped) atomicAdd((ull*)&a.dd_ff_meta[5], (ull)dropped);
-}
-
 __global__ void k_ff_add(uint32_t* t, int64_t bmask, int gens, int g, int64_t* meta, const ull* __restrict__ h,
                          int64_t n) {
   uint32_t dropped = 0;
@@ -2290,17 +2143,6 @@ int sw_graph_capture_process(const SwEngineArgs* ap, uint32_t* scratch4, int32_t
 int sw_graph_launch(void* exec, hipStream_t s) { return (int)hipGraphLaunch((hipGraphExec_t)exec, s); }
 
 int sw_graph_destroy(void* exec) { return exec ? (int)hipGraphExecDestroy((hipGraphExec_t)exec) : 0; }
-
-// Registry patch: scatter host-built packed slots (bulk load and incremental upserts).
-__global__ void k_reg_patch(SwRegSlot* reg, const int64_t* slots, const SwRegSlot* vals, int64_t n) {
-  for (int64_t i = (int64_t)BID * BLK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLK) reg[slots[i]] = vals[i];
-}
-
-int sw_registry_patch(SwRegSlot* reg, const int64_t* slots, const SwRegSlot* vals, int64_t n, hipStream_t s) {
-  if (n <= 0) return 0;
-  k_reg_patch<<<grid_for(n), BLK, 0, s>>>(reg, slots, vals, n);
-  return (int)hipGetLastError();
-}
 
 // Per-assignment device-state lookup: one thread per candidate (name id, kind) probes the state map
 // read-only for its (assignment, name, kind) key.  Name ids are dense (claim-time counter), so the

@@ -33,38 +33,12 @@
 #include "swindex.h"
 #include "swseg.h"
 #include "swtypes.h"
-
-typedef unsigned long long ull;
+#include "swblock.h"
 
 #define RS_BLK 256
 #define RS_ITEMS 16
 #define RS_TILE (RS_BLK * RS_ITEMS)
 #define RS_WAVES (RS_BLK / 64)
-
-__device__ __forceinline__ uint32_t ix_lane() { return threadIdx.x & 63; }
-
-// Block-wide exclusive scan of one u32 per thread (256 threads); *total = the sum.
-__device__ __forceinline__ uint32_t rs_block_scan(uint32_t v, uint32_t* red, uint32_t* total) {
-  const uint32_t lane = ix_lane(), wid = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d, 64);
-    if (lane >= (uint32_t)d) inc += o;
-  }
-  if (lane == 63) red[wid] = inc;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < RS_WAVES; ++w) {
-    const uint32_t x = red[w];
-    pre += (uint32_t)w < wid ? x : 0u;
-    tot += x;
-  }
-  __syncthreads();
-  *total = tot;
-  return inc - v + pre;
-}
 
 // ============================================================================ radix sort
 // Per pass, three dispatches and no cross-workgroup waiting: k_rs_count (each tile's digit counts,
@@ -111,7 +85,7 @@ __global__ __launch_bounds__(RS_BLK) void k_rs_count(const uint32_t* __restrict_
 
 // one workgroup per digit: exclusive prefix of the digit's tile counts, and its total
 __global__ __launch_bounds__(RS_BLK) void k_rs_offsets(const uint32_t* __restrict__ n_ptr, uint32_t* st_words, int64_t cap) {
-  __shared__ uint32_t red[RS_WAVES];
+  __shared__ uint32_t red[RS_WAVES + 1];
   const RsState st = rs_state(st_words, cap);
   const uint32_t n = *n_ptr;
   const int64_t ntiles = ((int64_t)n + RS_TILE - 1) / RS_TILE;
@@ -121,7 +95,7 @@ __global__ __launch_bounds__(RS_BLK) void k_rs_offsets(const uint32_t* __restric
     const int64_t t = t0 + threadIdx.x;
     const uint32_t v = t < ntiles ? st.hist[t * 256 + d] : 0u;
     uint32_t tot;
-    const uint32_t pre = rs_block_scan(v, red, &tot);
+    const uint32_t pre = block_excl_scan(v, &tot, red);
     if (t < ntiles) st.off[t * 256 + d] = run + pre;
     run += tot;
   }
@@ -135,7 +109,7 @@ struct RsLds {
   uint32_t ls[256];         // where a digit's run starts in the staged tile
   uint32_t run[256];        // ranked so far per digit
   uint32_t gb[256];         // where the tile's run of a digit starts in the output
-  uint32_t red[RS_WAVES];
+  uint32_t red[RS_WAVES + 1];
 };
 
 __global__ __launch_bounds__(RS_BLK) void k_rs_scatter(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
@@ -148,7 +122,7 @@ __global__ __launch_bounds__(RS_BLK) void k_rs_scatter(const uint32_t* __restric
   const int64_t tile = blockIdx.x;
   const int64_t base = tile * RS_TILE;
   if (base >= (int64_t)n) return;
-  const uint32_t t = threadIdx.x, lane = ix_lane(), wid = t >> 6;
+  const uint32_t t = threadIdx.x, lane = lane_id(), wid = t >> 6;
   const uint32_t mask = (1u << dbits) - 1u;
   uint32_t K[RS_ITEMS], V[RS_ITEMS];
 #pragma unroll
@@ -159,9 +133,9 @@ __global__ __launch_bounds__(RS_BLK) void k_rs_scatter(const uint32_t* __restric
     V[k] = ok ? vin[i] : 0u;
   }
   uint32_t gtot, ctot;
-  const uint32_t gpre = rs_block_scan(t <= mask ? st.tot[t] : 0u, L.red, &gtot);
+  const uint32_t gpre = block_excl_scan(t <= mask ? st.tot[t] : 0u, &gtot, L.red);
   const uint32_t c = t <= mask ? st.hist[tile * 256 + t] : 0u;
-  L.ls[t] = rs_block_scan(c, L.red, &ctot);
+  L.ls[t] = block_excl_scan(c, &ctot, L.red);
   L.gb[t] = gpre + (t <= mask ? st.off[tile * 256 + t] : 0u);
   L.run[t] = 0;
 #pragma unroll
@@ -365,9 +339,9 @@ __global__ __launch_bounds__(IX_PREP_BLK) void k_ix_prep(SwIxArgs a) {
     const bool g0 = a.aux && (a.aux[j - 1].flags & SEGF_GEN), g1 = a.aux && (a.aux[j].flags & SEGF_GEN);
     bad |= (g0 && !g1) || (!g0 && !g1 && a.rows[j].assignment < a.rows[j - 1].assignment);
   }
-  if (__ballot(bad) && ix_lane() == 0) atomicOr(&a.sc->unsorted, 1u);
+  if (__ballot(bad) && lane_id() == 0) atomicOr(&a.sc->unsorted, 1u);
   __syncthreads();
-  if (ix_lane() == 0 && nalt) atomicAdd(&lalt, nalt);
+  if (lane_id() == 0 && nalt) atomicAdd(&lalt, nalt);
   // context keys, one sweep per LDS pass
   const int npass = a.lds_all ? 1 : SIX_DIMS;
   for (int p = 0; p < npass; ++p) {
@@ -456,15 +430,11 @@ __global__ __launch_bounds__(IX_SCAN_BLK) void k_ix_scan(SwIxArgs a) {
     v[3] += nch;
     v[4] += nch > 1 ? nch : 0u;
   }
-  const uint32_t lane = ix_lane(), wid = threadIdx.x >> 6;
+  const uint32_t lane = lane_id(), wid = threadIdx.x >> 6;
   uint32_t inc[IX_NQ];
 #pragma unroll
   for (int q = 0; q < IX_NQ; ++q) {
-    inc[q] = v[q];
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t x = __shfl_up(inc[q], o, 64);
-      if (lane >= (uint32_t)o) inc[q] += x;
-    }
+    inc[q] = wave_incl_scan(v[q]);
     if (lane == 63) wsum[q][wid] = inc[q];
   }
   __syncthreads();
@@ -707,7 +677,7 @@ __device__ __forceinline__ void ix_sort16(ull (&K)[IX_SLOTS], uint32_t (&R)[IX_S
 // with the r-th newest in (od, orow)
 __device__ __forceinline__ void ix_take(ull (&K)[IX_SLOTS], uint32_t (&R)[IX_SLOTS], int n, uint32_t k, int64_t& od,
                                         uint32_t& orow) {
-  const uint32_t lane = ix_lane();
+  const uint32_t lane = lane_id();
   od = INT64_MIN;
   orow = 0;
   for (uint32_t r = 0; r < k; ++r) {
@@ -738,7 +708,7 @@ __device__ __forceinline__ void wave_minmax(int64_t& mn, int64_t& mx) {
 __device__ void ix_write_final(const SwIxArgs& a, const SwIxHdr& h, uint8_t* t, int d, uint32_t q, uint32_t k,
                                uint32_t cnt, uint32_t hoff, int64_t mn, int64_t mx, int64_t cd, uint32_t cr) {
   const uint32_t nh = cnt < SIX_HEADS ? cnt : SIX_HEADS;
-  const uint32_t lane = ix_lane();
+  const uint32_t lane = lane_id();
   if (lane < nh) {
     reinterpret_cast<uint32_t*>(t + h.off_heads[d])[hoff + lane] = cr;
     reinterpret_cast<int64_t*>(t + h.off_hdates[d])[hoff + lane] = cd;
@@ -759,7 +729,7 @@ __device__ void ix_write_final(const SwIxArgs& a, const SwIxHdr& h, uint8_t* t, 
 template <typename F>
 __device__ __forceinline__ int ix_load16(uint32_t nitems, F item, ull (&K)[IX_SLOTS], uint32_t (&R)[IX_SLOTS],
                                          int64_t& mn, int64_t& mx) {
-  const uint32_t lane = ix_lane();
+  const uint32_t lane = lane_id();
   int n = 0;
 #pragma unroll
   for (int s = 0; s < IX_SLOTS; ++s) {
@@ -794,18 +764,18 @@ __device__ void ix_chunk(const SwIxArgs& a, const SwIxHdr& h, uint8_t* t, int d,
   int64_t mn = INT64_MAX, mx = INT64_MIN;
   const int n = ix_load16(rows_c, [&](uint32_t i, int64_t& dt, uint32_t& row) { dt = bd[i]; row = br[i]; }, K, R, mn, mx);
   wave_minmax(mn, mx);
-  if (stp && ix_lane() == 0) stp[1] = __builtin_amdgcn_s_memrealtime();
+  if (stp && lane_id() == 0) stp[1] = __builtin_amdgcn_s_memrealtime();
   int64_t cd;
   uint32_t cr;
   ix_take(K, R, n, rows_c < SIX_HEADS ? rows_c : SIX_HEADS, cd, cr);
-  if (stp && ix_lane() == 0) stp[2] = __builtin_amdgcn_s_memrealtime();
+  if (stp && lane_id() == 0) stp[2] = __builtin_amdgcn_s_memrealtime();
   if (nch == 1) {
     ix_write_final(a, h, t, d, q, k, cnt, kr.hoff, mn, mx, cd, cr);
     return;
   }
   // a partial of a multi-chunk key (k_ix_merge folds them): min, max, its top-16
   int64_t* P = a.part + ((int64_t)d * a.pcap + kr.pch + c) * IX_PART_WORDS;
-  const uint32_t lane = ix_lane();
+  const uint32_t lane = lane_id();
   if (lane < SIX_HEADS) { P[2 + 2 * lane] = cd; P[3 + 2 * lane] = (int64_t)cr; }
   if (lane == 0) { P[0] = mn; P[1] = mx; }
 }
@@ -829,7 +799,7 @@ __device__ void ix_merge_key(const SwIxArgs& a, const SwIxHdr& h, uint8_t* t, in
       uint32_t R[IX_SLOTS];
       int64_t gmn = INT64_MAX, gmx = INT64_MIN;
       int n = 0;
-      const uint32_t lane = ix_lane();
+      const uint32_t lane = lane_id();
 #pragma unroll
       for (int s = 0; s < IX_SLOTS; ++s) {
         const uint32_t i = lane + 64u * s;
@@ -888,7 +858,7 @@ __global__ __launch_bounds__(IX_WBLK) void k_ix_heads(SwIxArgs a) {
     const uint32_t q = a.cmap[(int64_t)d * a.mcap + gc];
     const IxKeyRec kr = *reinterpret_cast<const IxKeyRec*>(a.krec + 2 * ((int64_t)d * SIX_KEYS + q));
     ix_chunk(a, h, t, d, q, kr, gc - kr.chunk0);
-    if (a.stamps && ix_lane() == 0) {
+    if (a.stamps && lane_id() == 0) {
       uint64_t* stp = a.stamps + 4 * ((int64_t)d * a.mcap + gc);
       stp[0] = t0;
       stp[3] = __builtin_amdgcn_s_memrealtime();
@@ -928,7 +898,7 @@ __global__ __launch_bounds__(IX_WBLK) void k_ix_finish(SwIxArgs a) {
       if (i != SIX_CHECKSUM_WORD) cs ^= seg_mix_word(reinterpret_cast<const ull*>(t)[i], i);
   }
   for (int off = 32; off >= 1; off >>= 1) cs ^= __shfl_xor(cs, off, 64);
-  if (ix_lane() == 0) red[threadIdx.x >> 6] = cs;
+  if (lane_id() == 0) red[threadIdx.x >> 6] = cs;
   __syncthreads();
   if (threadIdx.x == 0) {
     ull x = 0;
@@ -985,7 +955,6 @@ int64_t sw_seg_index_scratch_words(int64_t cap, int64_t nk_total) {
 int64_t sw_seg_index_max_bytes(int64_t rows) { return (int64_t)six_max_bytes((uint64_t)rows); }
 
 // stamps buffer words of sw_seg_index (4 per heads chunk, every dimension)
-int64_t sw_seg_index_stamp_words(int64_t cap) { return 4ll * SIX_DIMS * ix_mcap(cap); }
 
 // Build the index trailer of the block k_seg_encode just wrote (same stream, same arguments) and
 // append it to the block.  nk[d]: key space of dimension d ((max context id + 1) << 3 over the

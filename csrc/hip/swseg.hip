@@ -25,6 +25,7 @@
 #include <type_traits>
 #include "swtypes.h"
 #include "swseg.h"
+#include "swblock.h"
 
 // Workgroup geometry: SW_SEG_SBLK threads per page (RPT = 1024 / SBLK rows each); SW_SEG_MIN_WAVES
 // asks the compiler for at least that many waves per SIMD (a VGPR budget).  Measured in
@@ -42,8 +43,6 @@
 #define RPT (SEG_PAGE_ROWS / SBLK)
 #define HEAP_LDS 26624     // heap bytes a page can stage in LDS (the column staging union); larger heaps
                            // are gathered straight from the raw batch
-
-typedef unsigned long long ull;
 
 struct SwSegArgs {
   const SwOutRec* rows;        // this step's rows (device), persisted order
@@ -72,8 +71,6 @@ struct SwSegArgs {
 #define LB_INC (2ull << 62)
 #define LB_VAL ((1ull << 62) - 1)
 #define LB_SPIN_LIMIT (1u << 22)
-
-__device__ __forceinline__ uint32_t lane64() { return threadIdx.x & 63; }
 
 __device__ __forceinline__ ull wmin(ull v) {
 #pragma unroll
@@ -286,7 +283,7 @@ __device__ __forceinline__ uint32_t dpp_scan(uint32_t v) {
 // Wave partial of one reduction slot (wave-uniform, stored once); block_finish combines the waves.
 __device__ __forceinline__ void wave_put(SegLds& L, int slot, ull v, bool mx) {
   const ull r = mx ? dpp_minmax<true>(v) : dpp_minmax<false>(v);
-  if (lane64() == 0) L.red[threadIdx.x >> 6][slot] = r;
+  if (lane_id() == 0) L.red[threadIdx.x >> 6][slot] = r;
 }
 
 // Slots [0, ns): bit i of maxmask = max, else min.  Two barriers; L.res valid for every thread after.
@@ -538,7 +535,7 @@ __device__ __forceinline__ void seg_encode_page(const SwSegArgs& a, SegLds& L) {
     }
   }
   {
-    const uint32_t lane = lane64(), wid = threadIdx.x >> 6;
+    const uint32_t lane = lane_id(), wid = threadIdx.x >> 6;
     uint32_t hb = 0;
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
@@ -650,7 +647,7 @@ __device__ __forceinline__ void seg_encode_page(const SwSegArgs& a, SegLds& L) {
   for (uint32_t w = threadIdx.x; w < 2u * SEG_PAGE_ROWS; w += SBLK) (&L.u.st.vals[0][0])[w] = 0;
   // ---- the page's offset in the block: decoupled look-back by wave 0, 64 predecessors per round
   if (threadIdx.x < 64) {
-    const uint32_t lane = lane64();
+    const uint32_t lane = lane_id();
     const ull size = L.page_size;
     ull excl = 0;
     bool failed = false;
@@ -909,7 +906,7 @@ __device__ __forceinline__ void seg_encode_page(const SwSegArgs& a, SegLds& L) {
   }
   cs = wxor(cs);
   __syncthreads();
-  if (lane64() == 0) L.red[threadIdx.x >> 6][0] = cs;
+  if (lane_id() == 0) L.red[threadIdx.x >> 6][0] = cs;
   __syncthreads();
   if (threadIdx.x == 0) {
     ull t = 0;

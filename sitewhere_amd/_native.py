@@ -30,7 +30,7 @@ _NATIVE_SRC = [CSRC / "native" / "swnative.cpp", CSRC / "native" / "swcpuengine.
                CSRC / "native" / "swindex.cpp", CSRC / "native" / "swroute.cpp", CSRC / "native" / "swsandbox.cpp", CSRC / "native" / "swjson.cpp",
                CSRC / "native" / "swrowjson.cpp"]
 _GPU_SRC = [CSRC / "hip" / "swgpu.hip", CSRC / "hip" / "swseg.hip", CSRC / "hip" / "swindex.hip"]
-_HEADERS = sorted((CSRC / "include").glob("*.h"))
+_HEADERS = sorted((CSRC / "include").glob("*.h")) + sorted((CSRC / "hip").glob("*.h"))
 
 _lock = threading.Lock()
 _native = None
@@ -308,7 +308,6 @@ def gpu():
         _proto(lib, "sw_phase_partition", c_int32, P, P)
         _proto(lib, "sw_phase_unpack", c_int32, P, P)
         _proto(lib, "sw_phase_process", c_int32, P, P, P)
-        _proto(lib, "sw_registry_patch", c_int32, P, P, P, c_int64, P)
         _proto(lib, "sw_pip_batch", c_int32, P, c_int64, P, P, c_int64, P, P)
         _proto(lib, "sw_store_filter", c_int32, P, P, P, c_int64, c_int32, P, c_int64, c_int64, c_int64, P, c_int64,
                P, P)
@@ -338,7 +337,6 @@ def gpu():
         _proto(lib, "sw_seg_index_max_bytes", c_int64, c_int64)
         _proto(lib, "sw_seg_index", c_int32, P, P, P, P, P, c_int64, P, c_int64, P, P, c_int64, P, c_int64, P, P,
                c_int64, P, P)
-        _proto(lib, "sw_seg_index_stamp_words", c_int64, c_int64)
         _proto(lib, "sw_ff_add", c_int32, P, c_int64, c_int64, c_int64, P, P, c_int64, P)
         _proto(lib, "sw_ff_clear", c_int32, P, c_int64, c_int64, c_int64, P)
         _proto(lib, "sw_reject_refs", c_int32, P, P, P, c_int64, P, P, c_int64, P, c_int64, P)

@@ -1,8 +1,9 @@
 """ctypes mirror of ``SwEngineArgs`` (csrc/include/swengine.h).
 
 Every field is 8 bytes; the order below must match the header exactly.
-``tests/test_columnar.py`` compares ``ctypes.sizeof(SwEngineArgs)`` with the
-library's own ``sizeof`` (``sw_abi_sizes``).
+``tests/test_columnar.py`` compares the (name, kind) sequence with the header's,
+``tests/test_gpu_engine.py`` ``ctypes.sizeof(SwEngineArgs)`` with the library's
+own ``sizeof`` (``sw_abi_sizes``).
 """
 from __future__ import annotations
 

@@ -143,7 +143,8 @@ class GpuInboundEngine(EngineBase):
         ntiles = (c.rec_cap + tile - 1) // tile
         mtiles = (c.max_msgs + tile - 1) // tile
         ptiles = (c.carry_cap + c.rec_cap + tile - 1) // tile     # partition input: carry + records
-        # single-pass scans keep u64 look-back state (2 + tiles words) in it, zeroed by each scan
+        # the partition's count scan keeps one u32 sum per 1024 counts in it, rewritten by every scan
+        # (no state to zero or re-arm); the process phase asks for 2 * ntiles words
         scan_tmp = 2 * (max(ptiles * 2 * max(1, c.world), mtiles, 2 * ntiles) + 64)
         self.t = t = {}
         # decode
