@@ -1,7 +1,9 @@
-// Device-side scan primitives shared by swgpu.hip, swseg.hip and swindex.hip.  Wave64 throughout.
+// Device-side scan primitives and the step-snapshot writer shared by swgpu.hip, swseg.hip and
+// swindex.hip.  Wave64 throughout.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "swengine.h"
 
 typedef unsigned long long ull;
 
@@ -53,6 +55,25 @@ __device__ __forceinline__ uint32_t block_sum_prefix(const uint32_t* v, int64_t 
   uint32_t tot;
   block_excl_scan<uint32_t, WAVES>(s, &tot, lds);
   return tot;
+}
+
+// The one writer of the end-of-step snapshot (SwStepSnapshot, swengine.h): thread t stores u32 word t
+// of the record in mapped host memory, so a workgroup's first 26 threads write it whole.  A step that
+// produced nothing leaves only the carry counts.  block_meta: the encoder's three result words
+// (SEG_ST_BYTES.., swseg.h) or null; BLOCK_WORDS = false leaves the block words to the caller
+// (k_seg_encode's last workgroup stores them from the values it publishes).
+template <bool BLOCK_WORDS>
+__device__ __forceinline__ void step_snapshot_write(SwStepSnapshot* rec, uint32_t t, const uint32_t* scalars,
+                                                    const uint32_t* block_meta, const uint32_t* rej_cnt,
+                                                    const uint32_t* n_carry, bool produced) {
+  constexpr uint32_t BLOCK = offsetof(SwStepSnapshot, block_bytes) / 4, CARRY = offsetof(SwStepSnapshot, n_carry) / 4,
+                     REJ = offsetof(SwStepSnapshot, rej_refs) / 4, PAD = offsetof(SwStepSnapshot, pad) / 4;
+  static_assert(BLOCK == SW_SC_WORDS && CARRY == BLOCK + 6 && REJ == CARRY + 2 && PAD == REJ + 2, "word ladder");
+  uint32_t* w = reinterpret_cast<uint32_t*>(rec);
+  if (t < BLOCK) w[t] = produced ? scalars[t] : 0u;
+  else if (t < CARRY) { if (BLOCK_WORDS) w[t] = (produced && block_meta) ? block_meta[t - BLOCK] : 0u; }
+  else if (t == CARRY || t == CARRY + 1) w[t] = n_carry ? n_carry[t - CARRY] : 0u;
+  else if (t == REJ || t == REJ + 1) w[t] = (produced && rej_cnt) ? rej_cnt[t - REJ] : 0u;
 }
 
 // The stable LSD radix sort of swindex.hip, also the engine step's clustering sort (swgpu.hip).

@@ -1830,28 +1830,24 @@ int sw_reject_refs(const SwEngineArgs* ap, const uint8_t* raw, const uint32_t* m
   return (int)hipGetLastError();
 }
 
-// End-of-step snapshot into mapped host memory (one launch instead of one copy per value): the
-// step's u32 scalars (n_out at [7], n_rej at [5]) -> host[0..15]; the durable-block encoder's
-// (bytes, errors, first sequence) u64s -> host[16..21]; the reject-ref counters -> host[24..25].
+// End-of-step snapshot (SwStepSnapshot) into mapped host memory, one launch instead of one copy per
+// value: the step's scalars, the durable-block encoder's result words (seg_meta, or null), the re-key
+// carry counts and the reject-ref counters.
 __global__ void k_step_snapshot(const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ seg_meta,
                                 const uint32_t* __restrict__ rej_cnt, const uint32_t* __restrict__ n_carry,
-                                int produced, uint32_t* __restrict__ host) {
-  const uint32_t t = threadIdx.x;
-  if (t < 16) host[t] = produced ? scalars[t] : 0u;
-  else if (t < 22) host[t] = (produced && seg_meta) ? seg_meta[t - 16] : 0u;
-  else if (t == 22 || t == 23) host[t] = n_carry ? n_carry[t - 22] : 0u;     // re-key carry (both parities)
-  else if (t == 24 || t == 25) host[t] = (produced && rej_cnt) ? rej_cnt[t - 24] : 0u;
+                                int produced, SwStepSnapshot* __restrict__ host) {
+  step_snapshot_write<true>(host, threadIdx.x, scalars, seg_meta, rej_cnt, n_carry, produced != 0);
 }
 
 // The step's rejected records (SwEventRec, 80 B) and their statuses, gathered by rej_idx straight
-// into mapped host memory, bounded by the step's own reject count (scalars[5], read on the device) and
+// into mapped host memory, bounded by the step's own reject count (read on the device) and
 // `cap`: the host reads them after the step's event, with no copy call and no synchronising read of
 // the count first (GpuInboundEngine.submit_framed).
 __global__ __launch_bounds__(256) void k_reject_pack(const uint4* __restrict__ recs, const int32_t* __restrict__ rej_idx,
                                                       const uint8_t* __restrict__ status,
                                                       const uint32_t* __restrict__ scalars, uint32_t cap,
                                                       uint4* __restrict__ out, uint8_t* __restrict__ out_st) {
-  const uint32_t n = scalars[5] < cap ? scalars[5] : cap;
+  const uint32_t n = scalars[SW_SC_N_REJ] < cap ? scalars[SW_SC_N_REJ] : cap;
   const uint32_t words = 5;                     // sizeof(SwEventRec) / 16
   for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < n * words; w += gridDim.x * blockDim.x) {
     const uint32_t i = w / words, q = w - i * words;
@@ -1884,7 +1880,7 @@ int sw_memset_async(void* dst, int32_t v, int64_t n, hipStream_t s) {
 }
 
 int sw_step_snapshot(const uint32_t* scalars, const uint32_t* seg_meta, const uint32_t* rej_cnt,
-                     const uint32_t* n_carry, int32_t produced, uint32_t* host, hipStream_t s) {
+                     const uint32_t* n_carry, int32_t produced, SwStepSnapshot* host, hipStream_t s) {
   k_step_snapshot<<<1, 64, 0, s>>>(scalars, seg_meta, rej_cnt, n_carry, produced, host);
   return (int)hipGetLastError();
 }
@@ -2250,8 +2246,9 @@ static hsa_status_t sw_find_cpu(hsa_agent_t a, void*) {
   return HSA_STATUS_SUCCESS;
 }
 
-// engine: 0 = runtime's choice (hsa_amd_memory_async_copy), k>0 = SDMA engine bit (1 << (k-1)).
-int sw_sdma_copy(void* dst_host, const void* src_dev, int64_t bytes, int32_t engine, uint64_t* signal_out) {
+// One copy between device memory and pinned host memory on a copy engine.  to_host: dst is the host
+// side; engine: 0 = runtime's choice (hsa_amd_memory_async_copy), k>0 = SDMA engine bit (1 << (k-1)).
+static int sdma_copy(void* dst, const void* src, bool to_host, int64_t bytes, int32_t engine, uint64_t* signal_out) {
   if (g_cpu_agent.handle == 0) {
     hsa_status_t st = hsa_iterate_agents(sw_find_cpu, nullptr);
     if (st != HSA_STATUS_SUCCESS && st != HSA_STATUS_INFO_BREAK) return 1000 + (int)st;
@@ -2259,17 +2256,18 @@ int sw_sdma_copy(void* dst_host, const void* src_dev, int64_t bytes, int32_t eng
   }
   hsa_amd_pointer_info_t info;
   info.size = sizeof(info);
-  hsa_status_t st = hsa_amd_pointer_info(src_dev, &info, nullptr, nullptr, nullptr);
+  hsa_status_t st = hsa_amd_pointer_info(to_host ? src : dst, &info, nullptr, nullptr, nullptr);
   if (st != HSA_STATUS_SUCCESS) return 2000 + (int)st;
-  hsa_agent_t gpu_agent = info.agentOwner;
+  const hsa_agent_t gpu_agent = info.agentOwner;
+  const hsa_agent_t dst_agent = to_host ? g_cpu_agent : gpu_agent, src_agent = to_host ? gpu_agent : g_cpu_agent;
   hsa_signal_t sig;
   st = hsa_signal_create(1, 0, nullptr, &sig);
   if (st != HSA_STATUS_SUCCESS) return 3000 + (int)st;
   if (engine > 0) {
-    st = hsa_amd_memory_async_copy_on_engine(dst_host, g_cpu_agent, src_dev, gpu_agent, (size_t)bytes, 0, nullptr,
-                                             sig, (hsa_amd_sdma_engine_id_t)(1u << (engine - 1)), true);
+    st = hsa_amd_memory_async_copy_on_engine(dst, dst_agent, src, src_agent, (size_t)bytes, 0, nullptr, sig,
+                                             (hsa_amd_sdma_engine_id_t)(1u << (engine - 1)), true);
   } else {
-    st = hsa_amd_memory_async_copy(dst_host, g_cpu_agent, src_dev, gpu_agent, (size_t)bytes, 0, nullptr, sig);
+    st = hsa_amd_memory_async_copy(dst, dst_agent, src, src_agent, (size_t)bytes, 0, nullptr, sig);
   }
   if (st != HSA_STATUS_SUCCESS) {
     hsa_signal_destroy(sig);
@@ -2279,33 +2277,13 @@ int sw_sdma_copy(void* dst_host, const void* src_dev, int64_t bytes, int32_t eng
   return 0;
 }
 
+int sw_sdma_copy(void* dst_host, const void* src_dev, int64_t bytes, int32_t engine, uint64_t* signal_out) {
+  return sdma_copy(dst_host, src_dev, true, bytes, engine, signal_out);
+}
+
 // Host -> device on a copy engine (probe / H2D experiments): the mirror of sw_sdma_copy.
 int sw_sdma_h2d(void* dst_dev, const void* src_host, int64_t bytes, int32_t engine, uint64_t* signal_out) {
-  if (g_cpu_agent.handle == 0) {
-    hsa_status_t st = hsa_iterate_agents(sw_find_cpu, nullptr);
-    if (st != HSA_STATUS_SUCCESS && st != HSA_STATUS_INFO_BREAK) return 1000 + (int)st;
-    if (g_cpu_agent.handle == 0) return 999;
-  }
-  hsa_amd_pointer_info_t info;
-  info.size = sizeof(info);
-  hsa_status_t st = hsa_amd_pointer_info(dst_dev, &info, nullptr, nullptr, nullptr);
-  if (st != HSA_STATUS_SUCCESS) return 2000 + (int)st;
-  hsa_agent_t gpu_agent = info.agentOwner;
-  hsa_signal_t sig;
-  st = hsa_signal_create(1, 0, nullptr, &sig);
-  if (st != HSA_STATUS_SUCCESS) return 3000 + (int)st;
-  if (engine > 0) {
-    st = hsa_amd_memory_async_copy_on_engine(dst_dev, gpu_agent, src_host, g_cpu_agent, (size_t)bytes, 0, nullptr,
-                                             sig, (hsa_amd_sdma_engine_id_t)(1u << (engine - 1)), true);
-  } else {
-    st = hsa_amd_memory_async_copy(dst_dev, gpu_agent, src_host, g_cpu_agent, (size_t)bytes, 0, nullptr, sig);
-  }
-  if (st != HSA_STATUS_SUCCESS) {
-    hsa_signal_destroy(sig);
-    return 4000 + (int)st;
-  }
-  *signal_out = sig.handle;
-  return 0;
+  return sdma_copy(dst_dev, src_host, false, bytes, engine, signal_out);
 }
 
 int sw_sdma_wait(uint64_t handle) {
@@ -2327,6 +2305,7 @@ int sw_abi_sizes(int64_t* out) {
   out[7] = sizeof(SwMsSlot);
   out[8] = sizeof(SwWireRec);
   out[9] = sizeof(SwStrRef);
+  out[10] = sizeof(SwStepSnapshot);
   return 0;
 }
 

@@ -244,9 +244,9 @@ struct SwIxArgs {
   int64_t n_asg;
   uint8_t* out;              // the block
   int64_t out_cap;
-  uint64_t* seg_state;       // the encoder's state: [max_pages + 1] bytes, [+2] errors
+  uint64_t* seg_state;       // the encoder's state (SEG_ST_* words after the max_pages look-back words)
   int64_t max_pages;
-  uint32_t* snap_host;       // mapped end-of-step snapshot (bytes at [16..17]) or null
+  SwStepSnapshot* snap_host; // mapped end-of-step snapshot (its block bytes / errors are patched) or null
   int32_t nk[SIX_DIMS];      // key space per dimension ((max context id + 1) << 3), -1: not indexed
   int32_t nk_off[SIX_DIMS];  // each dimension's offset in a workgroup histogram row
   int32_t nk_total;          // histogram row length
@@ -290,7 +290,7 @@ __device__ __forceinline__ int32_t ix_ctx(const SwIxArgs& a, int32_t asg, int d)
   return d == 0 ? c.y : d == 1 ? c.z : c.w;
 }
 __device__ __forceinline__ bool ix_encoder_failed(const SwIxArgs& a) {
-  return a.seg_state[a.max_pages + 2] != 0;
+  return a.seg_state[a.max_pages + SEG_ST_ERRORS] != 0;
 }
 __device__ __forceinline__ void ix_range(const SwIxArgs& a, int64_t n, int64_t* r0, int64_t* r1) {
   const int64_t per = ((n + a.groups - 1) / a.groups + 63) & ~63ll;
@@ -914,13 +914,13 @@ __global__ __launch_bounds__(IX_WBLK) void k_ix_finish(SwIxArgs a) {
   const uint64_t bytes = sc->tstart + sc->h.bytes;
   if (ok) {
     reinterpret_cast<ull*>(a.out + sc->tstart)[SIX_CHECKSUM_WORD] = total_cs;
-    a.seg_state[a.max_pages + 1] = bytes;
-    if (a.snap_host) { a.snap_host[16] = (uint32_t)bytes; a.snap_host[17] = (uint32_t)(bytes >> 32); }
+    a.seg_state[a.max_pages + SEG_ST_BYTES] = bytes;
+    if (a.snap_host) a.snap_host->block_bytes = bytes;
   } else if (!ix_encoder_failed(a)) {
     // the trailer could not be built: a loud encoder error, never a block without its index
-    a.seg_state[a.max_pages + 2] += 1;
-    a.seg_state[a.max_pages + 1] = ~0ull;
-    if (a.snap_host) { a.snap_host[16] = ~0u; a.snap_host[17] = ~0u; a.snap_host[18] += 1; }
+    a.seg_state[a.max_pages + SEG_ST_ERRORS] += 1;
+    a.seg_state[a.max_pages + SEG_ST_BYTES] = ~0ull;
+    if (a.snap_host) { a.snap_host->block_bytes = ~0ull; a.snap_host->block_errors += 1; }
   }
   sc->cs = 0;
   sc->n_alt = 0;
@@ -962,7 +962,7 @@ int64_t sw_seg_index_max_bytes(int64_t rows) { return (int64_t)six_max_bytes((ui
 // u32[sw_seg_index_scratch_words(cap, sum of the non-negative nk)], zeroed at allocation.
 int sw_seg_index(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, const uint64_t* s_alt,
                  int64_t store_cap, const void* asg_ctx, int64_t n_asg, const int32_t* nk, uint8_t* out,
-                 int64_t out_cap, uint64_t* seg_state, int64_t max_pages, uint32_t* snap_host, uint32_t* scratch,
+                 int64_t out_cap, uint64_t* seg_state, int64_t max_pages, SwStepSnapshot* snap_host, uint32_t* scratch,
                  int64_t cap, uint64_t* stamps, hipStream_t s) {
   SwIxArgs a;
   a.stamps = stamps;

@@ -55,13 +55,12 @@ struct SwSegArgs {
   int64_t max_pages;
   uint64_t* stamps;            // profiling: [page * 16 + phase] s_memrealtime stamps (null: off)
   // end-of-step snapshot into mapped host memory, written by the last workgroup (what
-  // k_step_snapshot does in its own dispatch; null host: none): the step's u32 scalars -> host[0..15],
-  // this block's (bytes, errors, first sequence) -> host[16..21], the re-key carry counts ->
-  // host[22..23], the reject-ref counters -> host[24..25]
+  // k_step_snapshot does in its own dispatch; null host: none): the step's scalars, this block's
+  // result words, the re-key carry counts (or null), the reject-ref counters (or null)
   const uint32_t* snap_scalars;
   const uint32_t* snap_rej;
   const uint32_t* snap_carry;
-  uint32_t* snap_host;
+  SwStepSnapshot* snap_host;
 };
 
 // phase stamps of a page (profiling builds of the caller only: a null pointer costs a branch)
@@ -300,21 +299,7 @@ __device__ __forceinline__ void block_finish(SegLds& L, int ns, uint64_t maxmask
   __syncthreads();
 }
 
-// state = u64[max_pages + 8]: [0, max_pages) look-back words; then
-//   +0 ticket, +1 block bytes (out), +2 errors (out), +3 first store sequence (out),
-//   +4 bytes accumulator, +5 errors accumulator, +6 blocks done.
-// The workgroup that finishes last publishes the accumulators to the outputs and zeroes every
-// word the next launch relies on (look-back words, ticket, accumulators, done): no memset node
-// before each encode.  The allocation starts zeroed.
-#define SEG_ST_TICKET 0
-#define SEG_ST_BYTES 1
-#define SEG_ST_ERRORS 2
-#define SEG_ST_FIRST 3
-#define SEG_ST_BYTES_ACC 4
-#define SEG_ST_ERRORS_ACC 5
-#define SEG_ST_DONE 6
-#define SEG_ST_WORDS 8
-
+// state: the words after the look-back words are SEG_ST_* (swseg.h)
 __device__ __forceinline__ void seg_encode_page(const SwSegArgs& a, SegLds& L) {
   uint64_t* ticket = a.state + a.max_pages;
   uint64_t* bytes_out = ticket + SEG_ST_BYTES_ACC;
@@ -688,6 +673,7 @@ __device__ __forceinline__ void seg_encode_page(const SwSegArgs& a, SegLds& L) {
         page_off[page] = (uint32_t)base;
         if ((int64_t)page == np - 1) {
           page_off[np] = (uint32_t)(base + size);
+          if (!(np & 1)) page_off[np + 1] = 0;   // the table's pad word: the header checksum covers it
           SwSegBlockHdr* h = reinterpret_cast<SwSegBlockHdr*>(a.out);
           h->n_rows = (uint32_t)n;
           h->n_pages = (uint32_t)np;
@@ -938,9 +924,9 @@ __global__ __launch_bounds__(SBLK, SW_SEG_MIN_WAVES) void k_seg_encode(SwSegArgs
     st[SEG_ST_ERRORS] = errors;
     if (a.snap_host) {
       const ull first = lb_load(&st[SEG_ST_FIRST]);
-      a.snap_host[16] = (uint32_t)bytes; a.snap_host[17] = (uint32_t)(bytes >> 32);
-      a.snap_host[18] = (uint32_t)errors; a.snap_host[19] = (uint32_t)(errors >> 32);
-      a.snap_host[20] = (uint32_t)first; a.snap_host[21] = (uint32_t)(first >> 32);
+      a.snap_host->block_bytes = bytes;
+      a.snap_host->block_errors = errors;
+      a.snap_host->block_first_seq = first;
     }
     lb_store(&st[SEG_ST_TICKET], 0);
     lb_store(&st[SEG_ST_BYTES_ACC], 0);
@@ -948,58 +934,22 @@ __global__ __launch_bounds__(SBLK, SW_SEG_MIN_WAVES) void k_seg_encode(SwSegArgs
     lb_store(&st[SEG_ST_DONE], 0);
   }
   for (int64_t i = threadIdx.x; i < a.max_pages; i += SBLK) lb_store(&a.state[i], 0);
-  if (a.snap_host) {
-    const uint32_t t = threadIdx.x;
-    if (t < 16) a.snap_host[t] = a.snap_scalars[t];
-    else if (t == 22 || t == 23) a.snap_host[t] = a.snap_carry ? a.snap_carry[t - 22] : 0u;
-    else if (t == 24 || t == 25) a.snap_host[t] = a.snap_rej ? a.snap_rej[t - 24] : 0u;
-  }
+  if (a.snap_host)
+    step_snapshot_write<false>(a.snap_host, threadIdx.x, a.snap_scalars, nullptr, a.snap_rej, a.snap_carry, true);
 }
 
 extern "C" {
 
-// Encode this step's rows into `out`.  state = u64[max_pages + 8], zeroed when allocated and re-armed
-// by the kernel itself; afterwards state[max_pages + 1] = block bytes (~0 on error),
-// state[max_pages + 2] = errors, state[max_pages + 3] = the store sequence of the block's first row.
-int sw_seg_encode_stamped(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, uint8_t* out,
-                          int64_t out_cap, uint64_t* state, int64_t max_pages, uint64_t* stamps, hipStream_t s);
-
-static int seg_encode_launch(const SwSegArgs& a, hipStream_t s) {
-  const unsigned grid = (unsigned)(a.max_pages > 0 ? a.max_pages : 1);
-  k_seg_encode<<<grid, SBLK, 0, s>>>(a);
-  return (int)hipGetLastError();
-}
-
-int sw_seg_encode(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, uint8_t* out,
-                  int64_t out_cap, uint64_t* state, int64_t max_pages, hipStream_t s) {
-  return sw_seg_encode_stamped(rows, aux, raw, cursor, out, out_cap, state, max_pages, nullptr, s);
-}
-
-// Encode + the end-of-step snapshot in the same dispatch (see SwSegArgs.snap_*): the engine's
-// per-step path when it writes a durable block.
-int sw_seg_encode_snap(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, uint8_t* out,
-                       int64_t out_cap, uint64_t* state, int64_t max_pages, const uint32_t* scalars,
-                       const uint32_t* rej_cnt, const uint32_t* n_carry, uint32_t* host, hipStream_t s) {
-  SwSegArgs a;
-  a.rows = (const SwOutRec*)rows;
-  a.aux = (const SwSegAux*)aux;
-  a.raw = raw;
-  a.cursor = cursor;
-  a.out = out;
-  a.out_cap = out_cap;
-  a.state = state;
-  a.max_pages = max_pages;
-  a.stamps = nullptr;
-  a.snap_scalars = scalars;
-  a.snap_rej = rej_cnt;
-  a.snap_carry = n_carry;
-  a.snap_host = host;
-  return seg_encode_launch(a, s);
-}
-
-// Same, recording 16 phase stamps per page (s_memrealtime, 100 MHz) into stamps[max_pages * 16].
-int sw_seg_encode_stamped(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, uint8_t* out,
-                          int64_t out_cap, uint64_t* state, int64_t max_pages, uint64_t* stamps, hipStream_t s) {
+// Encode this step's rows into `out`.  state = u64[max_pages + SEG_ST_WORDS], zeroed when allocated
+// and re-armed by the kernel itself; afterwards its SEG_ST_BYTES / SEG_ST_ERRORS / SEG_ST_FIRST words
+// (swseg.h) hold the block bytes (~0 on error), the errors and the store sequence of the first row.
+// stamps (or null): 16 phase stamps per page (s_memrealtime, 100 MHz) into stamps[max_pages * 16].
+// host (or null): the end-of-step snapshot written in the same dispatch (see SwSegArgs.snap_*), the
+// engine's per-step path when it writes a durable block.
+static int seg_encode_launch(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, uint8_t* out,
+                             int64_t out_cap, uint64_t* state, int64_t max_pages, uint64_t* stamps,
+                             const uint32_t* scalars, const uint32_t* rej_cnt, const uint32_t* n_carry,
+                             SwStepSnapshot* host, hipStream_t s) {
   SwSegArgs a;
   a.rows = (const SwOutRec*)rows;
   a.aux = (const SwSegAux*)aux;
@@ -1010,11 +960,32 @@ int sw_seg_encode_stamped(const void* rows, const void* aux, const uint8_t* raw,
   a.state = state;
   a.max_pages = max_pages;
   a.stamps = stamps;
-  a.snap_scalars = nullptr;
-  a.snap_rej = nullptr;
-  a.snap_carry = nullptr;
-  a.snap_host = nullptr;
-  return seg_encode_launch(a, s);
+  a.snap_scalars = scalars;
+  a.snap_rej = rej_cnt;
+  a.snap_carry = n_carry;
+  a.snap_host = host;
+  const unsigned grid = (unsigned)(max_pages > 0 ? max_pages : 1);
+  k_seg_encode<<<grid, SBLK, 0, s>>>(a);
+  return (int)hipGetLastError();
+}
+
+int sw_seg_encode(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, uint8_t* out,
+                  int64_t out_cap, uint64_t* state, int64_t max_pages, hipStream_t s) {
+  return seg_encode_launch(rows, aux, raw, cursor, out, out_cap, state, max_pages, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, s);
+}
+
+int sw_seg_encode_snap(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, uint8_t* out,
+                       int64_t out_cap, uint64_t* state, int64_t max_pages, const uint32_t* scalars,
+                       const uint32_t* rej_cnt, const uint32_t* n_carry, SwStepSnapshot* host, hipStream_t s) {
+  return seg_encode_launch(rows, aux, raw, cursor, out, out_cap, state, max_pages, nullptr, scalars, rej_cnt, n_carry,
+                           host, s);
+}
+
+int sw_seg_encode_stamped(const void* rows, const void* aux, const uint8_t* raw, const int64_t* cursor, uint8_t* out,
+                          int64_t out_cap, uint64_t* state, int64_t max_pages, uint64_t* stamps, hipStream_t s) {
+  return seg_encode_launch(rows, aux, raw, cursor, out, out_cap, state, max_pages, stamps, nullptr, nullptr, nullptr,
+                           nullptr, s);
 }
 
 // Encoder aux of a step's rows from its records, for callers outside the engine (the engine's

@@ -5,6 +5,7 @@
 // allocates every buffer as a torch tensor (so the caching allocator owns HBM)
 // and passes raw pointers; the library never allocates.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "swtypes.h"
 
@@ -242,6 +243,36 @@ typedef struct SwEngineArgs {
   const SwMxTest* mtests;
   int64_t n_mtests;
 } SwEngineArgs;
+
+// A step's u32 scalar words (device counters the kernels write; SwEngineArgs points into them).
+// SC_* in sitewhere_amd/models/columnar.py mirrors the enum.
+enum {
+  SW_SC_N_RECS = 0,
+  SW_SC_N_NEW_NAMES,
+  SW_SC_OVERFLOW,
+  SW_SC_N_WORK,
+  SW_SC_N_OK,
+  SW_SC_N_REJ,
+  SW_SC_N_GEN,
+  SW_SC_N_OUT,
+  SW_SC_N_RULE,
+  SW_SC_WORDS = 16,
+};
+
+// End-of-step snapshot in mapped host memory, read by the host after the step's event with no copy
+// call (STEP_SNAPSHOT in sitewhere_amd/models/columnar.py mirrors it).  Written by k_step_snapshot,
+// or by k_seg_encode's last workgroup when the step encodes a durable block; the index build's last
+// workgroup then patches the block bytes and errors (step_snapshot_write in csrc/hip/swblock.h).
+typedef struct SwStepSnapshot {
+  uint32_t scalars[SW_SC_WORDS];
+  uint64_t block_bytes, block_errors, block_first_seq;  // the durable-block encoder's result words
+  uint32_t n_carry[2];                                  // re-key carry, both parities
+  uint32_t rej_refs, rej_bytes;                         // k_reject_refs counters
+  uint32_t pad[6];
+} SwStepSnapshot;
+static_assert(sizeof(SwStepSnapshot) == 128, "SwStepSnapshot is 32 u32 words");
+static_assert(offsetof(SwStepSnapshot, block_bytes) == 64 && offsetof(SwStepSnapshot, n_carry) == 88 &&
+              offsetof(SwStepSnapshot, rej_refs) == 96, "SwStepSnapshot layout");
 
 #define SW_N_STATS 24
 

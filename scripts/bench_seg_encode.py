@@ -29,7 +29,7 @@ def main():
     import torch
 
     from sitewhere_amd._native import gpu
-    from sitewhere_amd.models.columnar import EVENT_REC, OUT_REC, STR_REF
+    from sitewhere_amd.models.columnar import EVENT_REC, OUT_REC, SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, STR_REF
     from sitewhere_amd.persistence.segments import PAGE_ROWS, max_block_bytes, max_string_bytes
     from tests.test_segments import synth_rows
     lib = gpu()
@@ -52,7 +52,7 @@ def main():
     cap = max_block_bytes(n, max_string_bytes(n, len(raw)))
     pages = -(-n // PAGE_ROWS)
     blk = torch.zeros(cap, dtype=torch.uint8, device=d)
-    state = torch.zeros(pages + 8, dtype=torch.int64, device=d)
+    state = torch.zeros(pages + SEG_ST_WORDS, dtype=torch.int64, device=d)
     aux = torch.zeros(n * 32, dtype=torch.uint8, device=d)
     s = torch.cuda.current_stream(d)
     P = ctypes.c_void_p
@@ -65,7 +65,7 @@ def main():
         assert lib.sw_seg_encode(P(rows_t.data_ptr()), P(aux.data_ptr()), P(raw_t.data_ptr()), P(cursor.data_ptr()),
                                  P(blk.data_ptr()), cap, P(state.data_ptr()), pages, P(s.cuda_stream)) == 0
         s.synchronize()
-        nb0 = int(state[pages + 1].item())
+        nb0 = int(state[pages + SEG_ST_BYTES].item())
         ref_block = blk[:nb0].cpu().numpy().copy()
         from ctypes import c_int32, c_int64
         var = ctypes.CDLL(os.path.abspath(a.lib))
@@ -84,7 +84,7 @@ def main():
         s.synchronize()
         if r >= 2:
             times.append(1000.0 * e0.elapsed_time(e1))
-    nb, err, _ = (int(x) for x in state[pages + 1:pages + 4].cpu().numpy())
+    nb, err, _ = (int(x) for x in state[pages + SEG_ST_BYTES:pages + SEG_ST_FIRST + 1].cpu().numpy())
     assert err == 0, err
     if ref_block is not None:
         assert nb == len(ref_block) and np.array_equal(blk[:nb].cpu().numpy(), ref_block), "variant block differs"

@@ -210,7 +210,7 @@ def main():
     if os.environ.get("SW_PIN_REFERRERS") == "1":         # diagnostic: who holds the pooled row buffers
         import gc
         import sys as _sys
-        for _pin, arr in getattr(ib.engine, "_pin_pool", [])[:3]:
+        for _pin, arr in ib.engine._pins["rows"].pool[:3]:
             refs = gc.get_referrers(arr)
             print("pool buffer refcount", _sys.getrefcount(arr), [
                 (type(r).__name__, getattr(r, "shape", None), str(type(getattr(r, "base", None)).__name__))

@@ -427,7 +427,7 @@ def main():
     if ft:
         n_sub = max(1, k)
         trace["framed_phase_ms_per_submit"] = {kk: round(v * 1000 / n_sub, 3) for kk, v in ft.items()}
-    trace["pin_stats"] = {kk: v for kk, v in ib.engine.__dict__.items() if kk.startswith("pin_stats")}
+    trace["pin_stats"] = {kk: getattr(ib.engine, kk, None) for kk in ("pin_stats", "pin_stats_blocks")}
     cap = ecfg.dedup_filter_gens * ecfg.dedup_filter_ids
     out = {"metric": "tenant_soak_events_per_sec", "template": args.template, "devices": args.devices,
            "batch": args.batch, "p_unregistered": args.p_unregistered, "alt_ids": True, "via_bus": True,

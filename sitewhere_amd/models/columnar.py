@@ -114,6 +114,23 @@ MS_SLOT = np.dtype([("key", "<u8"), ("date", "<u8"), ("eid1", "<u8"), ("pad", "<
 ZONE_TEST = np.dtype([("zone", "<i4"), ("condition", "<i4"), ("alert_name_id", "<i4"), ("level", "<i4")])
 MX_TEST = np.dtype([("name_hash", "<u8"), ("lo", "<f8"), ("hi", "<f8")])     # SwMxTest
 
+# A step's u32 scalar words (SW_SC_* in swengine.h), in word order; SC_WORDS words are kept.
+SC_NAMES = ("n_recs", "n_new_names", "overflow", "n_work", "n_ok", "n_rej", "n_gen", "n_out", "n_rule")
+SC_N_RECS, SC_N_NEW_NAMES, SC_OVERFLOW, SC_N_WORK, SC_N_OK, SC_N_REJ, SC_N_GEN, SC_N_OUT, SC_N_RULE = range(9)
+SC_WORDS = 16
+
+# End-of-step snapshot the kernels write into mapped host memory (SwStepSnapshot in swengine.h).
+STEP_SNAPSHOT = np.dtype([
+    ("scalars", "<u4", (SC_WORDS,)), ("block_bytes", "<u8"), ("block_errors", "<u8"), ("block_first_seq", "<u8"),
+    ("n_carry", "<u4", (2,)), ("rej_refs", "<u4"), ("rej_bytes", "<u4"), ("pad", "<u4", (6,)),
+])
+assert STEP_SNAPSHOT.itemsize == 128
+
+# Durable-block encoder state (u64 words): the result words follow the max_pages look-back words
+# (SEG_ST_* in swseg.h) -- block bytes (~0 on error), errors, store sequence of the first row.
+SEG_ST_BYTES, SEG_ST_ERRORS, SEG_ST_FIRST = 1, 2, 3
+SEG_ST_WORDS = 8
+
 # Stats slots (SW_STAT_* in swengine.h).
 N_STATS = 24            # SW_N_STATS (csrc/include/swengine.h): slots of the stats arrays
 STAT_NAMES = [

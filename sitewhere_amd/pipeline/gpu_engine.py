@@ -22,17 +22,26 @@ import numpy as np
 import torch
 
 from .._native import gpu_gil as gpu_lib
-from ..models.columnar import EVENT_REC, N_STATS, OUT_REC, NAME_REF, OUT_REC_SIZE, ST_RECHECK, STR_REF, WIRE_REC
+from ..models.columnar import (EVENT_REC, N_STATS, OUT_REC, NAME_REF, OUT_REC_SIZE, SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK,
+                               SC_N_OUT, SC_N_RECS, SC_N_REJ, SC_N_RULE, SC_N_WORK, SC_NAMES, SC_OVERFLOW,
+                               SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC)
 from ..ops.engine_abi import SwEngineArgs
 from .config import EngineConfig
 from .bus_io import host_view
 from .engine_base import EngineBase, StepResult
+from .pinned_pool import PinnedPool
 
 _ALIGN = 64
 
 
 def _ptr(t: torch.Tensor) -> int:
     return t.data_ptr()
+
+
+def _chk(rc: int, name: str):
+    """Return code of native entry point ``name``: anything but 0 is an error."""
+    if rc:
+        raise RuntimeError(f"{name} failed ({rc})")
 
 
 class HostBuffer:
@@ -42,9 +51,7 @@ class HostBuffer:
         self.lib = lib
         self.nbytes = int(nbytes)
         h, d = ctypes.c_void_p(), ctypes.c_void_p()
-        rc = lib.sw_host_alloc(self.nbytes, ctypes.byref(h), ctypes.byref(d))
-        if rc:
-            raise RuntimeError(f"hipHostMalloc failed ({rc})")
+        _chk(lib.sw_host_alloc(self.nbytes, ctypes.byref(h), ctypes.byref(d)), "sw_host_alloc")
         self.host, self.dev = h.value, d.value
         self._arr = np.ctypeslib.as_array((ctypes.c_uint8 * self.nbytes).from_address(self.host))
 
@@ -54,21 +61,49 @@ class HostBuffer:
     def __del__(self):
         try:
             if self.host:
-                self.lib.sw_host_free(ctypes.c_void_p(self.host))
+                self.lib.sw_host_free(self.host)
                 self.host = None
         except Exception:
             pass
 
 
+class _CopyOut:
+    """One device -> pinned host copy in flight: on the copy engine (an HSA signal; no CUs), or
+    through the HIP runtime on ``stream`` (an event) when ``use_engine`` is false or the engine
+    refuses the copy.  ``engine_rc`` keeps the engine's refusal for the caller's policy; without a
+    ``stream`` a refused copy is not started at all."""
+    __slots__ = ("lib", "sig", "ev", "engine_rc")
+
+    def __init__(self, lib, dst: int, src: int, nbytes: int, engine: int = 0, stream=None, event=None,
+                 use_engine: bool = True):
+        self.lib, self.sig, self.ev, self.engine_rc = lib, None, None, 0
+        if use_engine:
+            h = ctypes.c_uint64()
+            self.engine_rc = lib.sw_sdma_copy(dst, src, nbytes, engine, ctypes.byref(h))
+            if self.engine_rc == 0:
+                self.sig = h.value
+                return
+        if stream is not None:
+            _chk(lib.sw_copy_d2h(dst, src, nbytes, stream.cuda_stream), "sw_copy_d2h")
+            self.ev = event if event is not None else torch.cuda.Event()
+            self.ev.record(stream)
+
+    def wait(self):
+        if self.sig is not None:
+            sig, self.sig = self.sig, None
+            _chk(self.lib.sw_sdma_wait(sig), "sw_sdma_wait")
+        elif self.ev is not None:
+            self.ev.synchronize()
+
+
 class _Submitted:
     """One batch in :meth:`GpuInboundEngine.submit_framed`'s pipeline."""
-    __slots__ = ("slot", "batch", "token", "small", "rows", "sig", "ev", "bmeta", "bbuf", "bsig", "bev", "now",
-                 "mapped")
+    __slots__ = ("slot", "batch", "token", "small", "rows", "rcopy", "bmeta", "bbuf", "bcopy", "now", "mapped")
 
     def __init__(self, slot, batch, token):
         self.slot, self.batch, self.token = slot, batch, token
-        self.small = self.rows = self.sig = self.ev = None
-        self.bmeta = self.bbuf = self.bsig = self.bev = None
+        self.small = self.rows = self.rcopy = None      # rows: pinned buffer; rcopy: its _CopyOut
+        self.bmeta = self.bbuf = self.bcopy = None      # the durable block's
         self.now = 0
         self.mapped = False             # step snapshot + rejects written into the slot's mapped host memory
 
@@ -80,9 +115,25 @@ def _host_addr(buf) -> int:
     return np.frombuffer(buf, np.uint8).ctypes.data
 
 
-def _chk(rc: int):
-    if rc:
-        raise RuntimeError(f"HIP stream call failed ({rc})")
+class _Staging:
+    """Device (raw, varint lengths, offsets) buffers of one framed batch, grown on demand."""
+
+    def __init__(self, e: "GpuInboundEngine"):
+        self.e, self.bufs = e, None
+
+    def get(self, nb: int, nl: int, before_realloc=None):
+        e, cur = self.e, self.bufs
+        if cur is None or cur[0].numel() < nb or cur[1].numel() < nl:
+            if before_realloc is not None:
+                before_realloc()                    # the old buffers may still be read
+            # grow geometrically: coalesced steps vary in size, and a reallocation per new maximum
+            # (device memory + a sync) would land in the middle of a burst
+            grow = 2 * cur[0].numel() if cur is not None else 0
+            cur = self.bufs = (
+                torch.empty(max(nb, grow, int(e._stg_hint)), dtype=torch.uint8, device=e.device),
+                torch.empty(max(nl, 5 * e.cfg.max_msgs + 64), dtype=torch.uint8, device=e.device),
+                torch.empty(e.cfg.max_msgs + 1, dtype=torch.int32, device=e.device))
+        return cur
 
 
 class _FramedSlots:
@@ -103,24 +154,21 @@ class _FramedSlots:
         for ev in self.ev_h2d + self.ev_comp:      # created now (torch creates them on first record):
             ev.record(self.h2d)                    # the submit path passes their raw handles natively
         self.h2d.synchronize()
-        self.bufs = [None] * self.SLOTS
+        self.bufs = [_Staging(e) for _ in range(self.SLOTS)]
+        # per-slot mapped host memory of the step snapshot, the rejected records and their statuses
+        self.snap = {}
         self.inflight = deque()
         self.k = 0
         self.no_sdma = False
 
     def buffers(self, b: int, nb: int, nl: int):
-        e = self.e
-        cur = self.bufs[b]
-        if cur is None or cur[0].numel() < nb or cur[1].numel() < nl:
-            self.ev_comp[b].synchronize()           # the old slot buffers may still be read
-            # grow geometrically: coalesced steps vary in size, and a reallocation per new maximum
-            # (device memory + a sync) would land in the middle of a burst
-            grow = 2 * cur[0].numel() if cur is not None else 0
-            cur = self.bufs[b] = (
-                torch.empty(max(nb, grow, int(getattr(e, "_stg_hint", 0))), dtype=torch.uint8, device=e.device),
-                torch.empty(max(nl, 5 * e.cfg.max_msgs + 64), dtype=torch.uint8, device=e.device),
-                torch.empty(e.cfg.max_msgs + 1, dtype=torch.int32, device=e.device))
-        return cur
+        return self.bufs[b].get(nb, nl, self.ev_comp[b].synchronize)
+
+    def copy_out(self, dst: int, src: int, nbytes: int) -> _CopyOut:
+        """Copy engine, or -- once it has refused a copy on this node -- the HIP runtime on ``d2h``."""
+        c = _CopyOut(self.e.lib, dst, src, nbytes, 0, self.d2h, use_engine=not self.no_sdma)
+        self.no_sdma = self.no_sdma or bool(c.engine_rc)
+        return c
 
 
 class GpuInboundEngine(EngineBase):
@@ -129,6 +177,7 @@ class GpuInboundEngine(EngineBase):
         self.lib = gpu_lib()
         self.device = torch.device(device)
         self.group = group
+        self._fp = None                        # submit_framed(): _FramedSlots, made on first use
         d = self.device
         c = cfg
         i32, i64, u8 = torch.int32, torch.int64, torch.uint8
@@ -156,7 +205,7 @@ class GpuInboundEngine(EngineBase):
         t["seen_key"] = z(c.name_slots, i64)
         t["new_names"] = z(c.names_cap * NAME_REF.itemsize, u8)
         t["vlen_tmp"] = z(2 * ((5 * c.max_msgs + tile - 1) // tile) + 64, i32)   # varint framing scan
-        t["scalars"] = z(64, i32)  # n_recs, n_new_names, overflow, n_work, n_ok, n_rej, n_gen, n_out, n_rule
+        t["scalars"] = z(64, i32)  # the step's SC_* words (models/columnar.py)
         # shuffle
         if c.world > 1:
             # send slabs are double-buffered (the pipelined exchange of batch k reads one while batch
@@ -259,11 +308,11 @@ class GpuInboundEngine(EngineBase):
         a.rank, a.world = c.rank, c.world
         a.msg_cnt, a.msg_evoff = _ptr(t["msg_cnt"]), _ptr(t["msg_evoff"])
         a.scan_tmp, a.scan_tmp_len = _ptr(t["scan_tmp"]), scan_tmp
-        a.recs, a.rec_cap, a.n_recs = _ptr(t["recs"]), c.rec_cap, S(0)
+        a.recs, a.rec_cap, a.n_recs = _ptr(t["recs"]), c.rec_cap, S(SC_N_RECS)
         a.spans = _ptr(t["spans"])
         a.seen_key, a.seen_mask = _ptr(t["seen_key"]), c.name_slots - 1
-        a.new_names, a.n_new_names, a.names_cap = _ptr(t["new_names"]), S(1), c.names_cap
-        a.overflow = S(2)
+        a.new_names, a.n_new_names, a.names_cap = _ptr(t["new_names"]), S(SC_N_NEW_NAMES), c.names_cap
+        a.overflow = S(SC_OVERFLOW)
         if c.world > 1:
             a.recv, a.shuf_cap, a.recv_cnt = _ptr(t["recv"]), c.shuf_cap, _ptr(t["recv_cnt"])
             if c.str_cap:
@@ -279,9 +328,9 @@ class GpuInboundEngine(EngineBase):
         else:
             a.work = a.recs
         a.str_drops = _ptr(t["str_drops"])
-        a.n_work = S(3)
+        a.n_work = S(SC_N_WORK)
         a.status, a.ev_dev, a.ev_asg = _ptr(t["status"]), _ptr(t["ev_dev"]), _ptr(t["ev_asg"])
-        a.ok_idx, a.n_ok, a.rej_idx, a.n_rej = _ptr(t["ok_idx"]), S(4), _ptr(t["rej_idx"]), S(5)
+        a.ok_idx, a.n_ok, a.rej_idx, a.n_rej = _ptr(t["ok_idx"]), S(SC_N_OK), _ptr(t["rej_idx"]), S(SC_N_REJ)
         a.cmp_tmp = _ptr(t["cmp_tmp"])
         if c.cluster:
             a.cl_keys, a.cl_vals, a.cl_hist, a.cl_bits = _ptr(t["cl_keys"]), _ptr(t["cl_vals"]), _ptr(t["cl_hist"]), c.cl_bits
@@ -305,17 +354,16 @@ class GpuInboundEngine(EngineBase):
          a.s_v0, a.s_v1, a.s_v2, a.s_alt, a.s_aux, a.s_batch) = [
             _ptr(st[k]) for k in ("etype", "level", "date", "recv", "dev", "asg", "cust", "area", "asset", "name",
                                   "v0", "v1", "v2", "alt", "aux", "batch")]
-        a.out, a.n_out = self.out_host[0].dev, S(7)
-        a.gen, a.gen_dev, a.gen_asg, a.n_gen, a.gen_cap = _ptr(t["gen"]), _ptr(t["gen_dev"]), _ptr(t["gen_asg"]), S(6), c.gen_cap
+        a.out, a.n_out = self.out_host[0].dev, S(SC_N_OUT)
+        a.gen, a.gen_dev, a.gen_asg, a.n_gen, a.gen_cap = _ptr(t["gen"]), _ptr(t["gen_dev"]), _ptr(t["gen_asg"]), S(SC_N_GEN), c.gen_cap
         a.zmask, a.ztile = _ptr(t["zmask"]), _ptr(t["ztile"])
         a.presence_missing_ms = 0
         a.presence_name_hash = self.presence_hash
         a.stats = _ptr(t["stats"])
         a.sp = _ptr(t["sp"])
-        self._rule_scratch = S(8)
+        self._rule_scratch = S(SC_N_RULE)
         # hipGraph of the process phase: captured on first use, replayed each step, re-captured
         # whenever a by-value argument of its kernels changes (zone rules)
-        import os
         self.use_graph = os.environ.get("SW_GRAPH", "1") != "0"
         self._graph = None
         self._cap_stream = torch.cuda.Stream(self.device) if self.use_graph else None
@@ -332,6 +380,17 @@ class GpuInboundEngine(EngineBase):
         self._ev_x = torch.cuda.Event()
         self._graph_nu = None                  # process graph without unpack (pipelined rounds)
         self._apply_zone_ptrs()
+        # host-side state of the framed / durable-block paths; buffers are allocated on first use
+        self._raw_bytes = 0                    # bound of the current batch's strings (block encoder)
+        self._stg = None                       # step(): pinned + device staging of a host batch
+        self._stg_hint = 0                     # expected raw bytes per batch (sizes the staging buffers)
+        self._stg_framed = _Staging(self)      # step_framed()
+        self._segs, self._aux_dev, self._rej_refs = {}, {}, {}      # per outbound slot
+        self._ix_scratch = None
+        self._carry_seen = None                # re-key carry of the pipelined runner's last snapshot
+        from ..persistence.segments import max_block_bytes
+        self._pins = {"rows": PinnedPool(out_cap * OUT_REC_SIZE, self.PIN_POOL, self.PIN_SPILL),
+                      "blocks": PinnedPool(max_block_bytes(out_cap), self.PIN_POOL_BLOCKS, self.PIN_SPILL)}
 
     # ------------------------------------------------------------------ control-plane hooks
     def _h2d(self, dst: torch.Tensor, src: np.ndarray):
@@ -414,7 +473,7 @@ class GpuInboundEngine(EngineBase):
         for attr in ("_graph", "_graph_nu"):
             if getattr(self, attr, None) is not None:
                 self._sync_streams()
-                self.lib.sw_graph_destroy(ctypes.c_void_p(getattr(self, attr)))
+                self.lib.sw_graph_destroy(getattr(self, attr))
                 setattr(self, attr, None)
 
     # ------------------------------------------------------------------ data plane
@@ -438,7 +497,7 @@ class GpuInboundEngine(EngineBase):
             raise ValueError(f"batch of {n_msgs} payloads exceeds EngineConfig.max_msgs={self.cfg.max_msgs}")
         a = self.args
         a.raw, a.msg_off, a.n_msgs, a.now_ms = _ptr(raw_dev), _ptr(off_dev), int(n_msgs), int(now_ms)
-        self._raw_bytes = int(raw_dev.numel())      # bound of the batch's strings (block encoder)
+        self._raw_bytes = int(raw_dev.numel())
 
     def _set_step_params(self, now_ms, presence=False, out_sel=None, out_to_device=False):
         """Stream-ordered SwStepParams of the next process phase (receive time, batch, presence, rows)."""
@@ -453,17 +512,15 @@ class GpuInboundEngine(EngineBase):
         # row's encoder aux beside it
         aux = _ptr(self._aux_buffer(sel)) if out_to_device else 0
         # strings: the raw batch on one rank; the exchanged string slabs (work_str) on several
-        raw_bytes = getattr(self, "_raw_bytes", 0) if self.world == 1 else self.world * self.cfg.str_cap
-        rc = self.lib.sw_set_step_params(ctypes.c_void_p(a.sp), int(now_ms), a.batch_seq, a.presence_missing_ms,
-                                         ctypes.c_void_p(a.out), ctypes.c_void_p(aux), int(raw_bytes), self._stream())
-        if rc:
-            raise RuntimeError(f"sw_set_step_params failed ({rc})")
+        raw_bytes = self._raw_bytes if self.world == 1 else self.world * self.cfg.str_cap
+        _chk(self.lib.sw_set_step_params(a.sp, int(now_ms), a.batch_seq, a.presence_missing_ms, a.out, aux,
+                                         int(raw_bytes), self._stream()), "sw_set_step_params")
         return sel
 
     # The three phases of a step (split so a multi-rank step can be driven without torch.distributed,
     # e.g. the loopback test that runs W engine shards on one GPU).
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
 
     def _sync_streams(self):
         """Wait for this engine's work only: the caller's current stream plus the engine's own
@@ -474,27 +531,21 @@ class GpuInboundEngine(EngineBase):
         for s in (getattr(self, "_comm", None), getattr(self, "_cap_stream", None)):
             if s is not None:
                 s.synchronize()
-        fp = self.__dict__.get("_fp")
-        if fp is not None:
-            fp.h2d.synchronize()
-            fp.d2h.synchronize()
+        if self._fp is not None:
+            self._fp.h2d.synchronize()
+            self._fp.d2h.synchronize()
 
     def frame_varint(self, lens_dev: torch.Tensor, nbytes: int, n_msgs: int, off_dev: torch.Tensor, raw_bytes: int):
         """Rebuild u32 payload offsets from the varint length stream on the current stream."""
         if n_msgs > self.cfg.max_msgs or nbytes > lens_dev.numel() or off_dev.numel() < n_msgs + 1:
             raise ValueError("varint framing buffers too small for this batch")
-        rc = self.lib.sw_frame_varint(ctypes.c_void_p(_ptr(lens_dev)), int(nbytes), int(n_msgs),
-                                      ctypes.c_void_p(_ptr(off_dev)), int(raw_bytes),
-                                      ctypes.c_void_p(_ptr(self.t["vlen_tmp"])), self.t["vlen_tmp"].numel(),
-                                      self._stream())
-        if rc:
-            raise RuntimeError(f"sw_frame_varint failed ({rc})")
+        tmp = self.t["vlen_tmp"]
+        _chk(self.lib.sw_frame_varint(_ptr(lens_dev), int(nbytes), int(n_msgs), _ptr(off_dev), int(raw_bytes),
+                                      _ptr(tmp), tmp.numel(), self._stream()), "sw_frame_varint")
 
     def phase_decode(self):
         ap = ctypes.byref(self.args)
-        rc = self.lib.sw_phase_decode(ap, self._stream())
-        if rc:
-            raise RuntimeError(f"sw_phase_decode failed ({rc})")
+        _chk(self.lib.sw_phase_decode(ap, self._stream()), "sw_phase_decode")
         if self.world > 1:
             a = self.args
             sp, cp = self._send_par, self._carry_par
@@ -508,9 +559,7 @@ class GpuInboundEngine(EngineBase):
                 a.carry_spans, a.carry_str = _ptr(self.carry_spans[cp]), _ptr(self.carry_strs[cp])
                 a.spill_spans, a.spill_str = _ptr(self.carry_spans[1 - cp]), _ptr(self.carry_strs[1 - cp])
                 a.n_spill_str = _ptr(self.t["n_carry_str"]) + 4 * (1 - cp)
-            rc = self.lib.sw_phase_partition(ap, self._stream())
-            if rc:
-                raise RuntimeError(f"sw_phase_partition failed ({rc})")
+            _chk(self.lib.sw_phase_partition(ap, self._stream()), "sw_phase_partition")
             self._last_send_par = sp
             self._send_par, self._carry_par = 1 - sp, 1 - cp
 
@@ -525,15 +574,12 @@ class GpuInboundEngine(EngineBase):
         exchange_slabs(self.send_cnts[p], self.t["recv_cnt"], self.send_bufs[p], self.t["recv"], self.group, extra)
 
     def phase_unpack(self):
-        rc = self.lib.sw_phase_unpack(ctypes.byref(self.args), self._stream())
-        if rc:
-            raise RuntimeError(f"sw_phase_unpack failed ({rc})")
+        _chk(self.lib.sw_phase_unpack(ctypes.byref(self.args), self._stream()), "sw_phase_unpack")
 
     def _capture(self, with_unpack: bool):
         ex = ctypes.c_void_p()
-        rc = self.lib.sw_graph_capture_process(ctypes.byref(self.args), ctypes.c_void_p(self._rule_scratch),
-                                               int(with_unpack), ctypes.c_void_p(self._cap_stream.cuda_stream),
-                                               ctypes.byref(ex))
+        rc = self.lib.sw_graph_capture_process(ctypes.byref(self.args), self._rule_scratch, int(with_unpack),
+                                               self._cap_stream.cuda_stream, ctypes.byref(ex))
         if rc:
             import warnings
             warnings.warn(f"hipGraph capture of the process phase failed ({rc}); using direct launches")
@@ -552,16 +598,12 @@ class GpuInboundEngine(EngineBase):
                 setattr(self, attr, self._capture(unpack))
             g = getattr(self, attr)
             if g is not None:
-                rc = self.lib.sw_graph_launch(ctypes.c_void_p(g), self._stream())
-                if rc:
-                    raise RuntimeError(f"sw_graph_launch failed ({rc})")
+                _chk(self.lib.sw_graph_launch(g, self._stream()), "sw_graph_launch")
                 self.batch_seq += 1
                 return
         if unpack:
             self.phase_unpack()
-        rc = self.lib.sw_phase_process(ap, ctypes.c_void_p(self._rule_scratch), self._stream())
-        if rc:
-            raise RuntimeError(f"sw_phase_process failed ({rc})")
+        _chk(self.lib.sw_phase_process(ap, self._rule_scratch, self._stream()), "sw_phase_process")
         self.batch_seq += 1
 
     # ------------------------------------------------------------------ pipelined exchange (world > 1)
@@ -649,9 +691,8 @@ class GpuInboundEngine(EngineBase):
         return {"oversize": int(v[0])}
 
     def scalars(self) -> dict:
-        v = self.t["scalars"][:9].cpu().numpy()
-        return dict(n_recs=int(v[0]), n_new_names=int(v[1]), overflow=int(v[2]), n_work=int(v[3]), n_ok=int(v[4]),
-                    n_rej=int(v[5]), n_gen=int(v[6]), n_out=int(v[7]), n_rule=int(v[8]))
+        v = self.t["scalars"][:len(SC_NAMES)].cpu().numpy()
+        return {name: int(x) for name, x in zip(SC_NAMES, v)}
 
     def step(self, raw: np.ndarray, offs: np.ndarray, now_ms: int, presence: bool | None = None) -> StepResult:
         """Synchronous convenience step (tests, control-plane use): H2D, run, D2H, learn names."""
@@ -677,11 +718,9 @@ class GpuInboundEngine(EngineBase):
             self._no_framed_pending()
             raw_dev, off_dev = self._stage(raw, offs)
             self._set_batch(raw_dev, off_dev, n_msgs, now_ms)
-            rc = self.lib.sw_phase_decode(ctypes.byref(self.args), self._stream())
-            if rc:
-                raise RuntimeError(f"sw_phase_decode failed ({rc})")
+            _chk(self.lib.sw_phase_decode(ctypes.byref(self.args), self._stream()), "sw_phase_decode")
             self._sync_streams()
-            n = min(int(self.t["scalars"][0].item()), self.cfg.rec_cap)
+            n = min(int(self.t["scalars"][SC_N_RECS].item()), self.cfg.rec_cap)
             recs = self.t["recs"][:n * EVENT_REC.itemsize].cpu().numpy().view(EVENT_REC).copy()
             if not spans:
                 return recs
@@ -702,13 +741,7 @@ class GpuInboundEngine(EngineBase):
             raise ValueError("raw batch payload lacks its tail padding")
         with self._lock:
             self._no_framed_pending()
-            st = getattr(self, "_stg_framed", None)
-            if st is None or st[0].numel() < nb or st[1].numel() < nl:
-                st = self._stg_framed = (
-                    torch.empty(max(nb, int(getattr(self, "_stg_hint", 0))), dtype=torch.uint8, device=self.device),
-                    torch.empty(max(nl, 5 * self.cfg.max_msgs + 64), dtype=torch.uint8, device=self.device),
-                    torch.empty(self.cfg.max_msgs + 1, dtype=torch.int32, device=self.device))
-            dev_r, dev_l, dev_o = st
+            dev_r, dev_l, dev_o = self._stg_framed.get(nb, nl)
             with warnings.catch_warnings():       # read-only topic views: torch only reads them here
                 warnings.simplefilter("ignore", UserWarning)
                 pt = torch.frombuffer(batch.payload, dtype=torch.uint8) if nb else None
@@ -734,8 +767,7 @@ class GpuInboundEngine(EngineBase):
         return res
 
     def _no_framed_pending(self):
-        fp = self.__dict__.get("_fp")
-        if fp is not None and fp.inflight:
+        if self._fp is not None and self._fp.inflight:
             raise RuntimeError("a submitted framed batch is pending: drain_framed() before a synchronous step")
 
     def _stage(self, raw: np.ndarray, offs: np.ndarray):
@@ -743,9 +775,9 @@ class GpuInboundEngine(EngineBase):
         ~6 GB/s plus a fresh padded copy per batch).  Only for the synchronous :meth:`step`: the
         staging buffers are reused by the next call."""
         nb, no = len(raw) + _ALIGN, len(offs)
-        st = getattr(self, "_stg", None)
+        st = self._stg
         if st is None or st[0].numel() < nb or st[1].numel() < no:
-            cap_b = max(nb, int(getattr(self, "_stg_hint", 0)))
+            cap_b = max(nb, int(self._stg_hint))
             pin_r = torch.empty(cap_b, dtype=torch.uint8).pin_memory()
             pin_o = torch.empty(max(no, self.cfg.max_msgs + 1), dtype=torch.int32).pin_memory()
             st = self._stg = (pin_r, pin_o, torch.empty(cap_b, dtype=torch.uint8, device=self.device),
@@ -759,63 +791,18 @@ class GpuInboundEngine(EngineBase):
         dev_o[:no].copy_(pin_o[:no], non_blocking=True)
         return dev_r[:nb], dev_o[:no]
 
-    ROW_HEADROOM = 1 << 16      # bytes kept free in front of the rows: a columnar batch header is
-                                # written there, making header + rows one contiguous payload
-
-    def _pinned_out(self, nbytes: int, kind: str = "rows"):
-        """A pinned host buffer (torch tensor + its full numpy view) with ``ROW_HEADROOM`` bytes in
-        front of the rows, that no earlier StepResult still references: a live ``result.out`` view
-        pins its base array, so results are returned without a copy and without fresh pageable pages
-        per step.  Returns (tensor, array, pooled); a result whose buffer is not pooled must not be
-        retained (``StepResult.frame_base`` is left unset)."""
-        import sys
-        need = nbytes + self.ROW_HEADROOM
-        sfx = "" if kind == "rows" else "_" + kind
-        pool = self.__dict__.setdefault("_pin_pool" + sfx, [])
-        spill = self.__dict__.setdefault("_pin_spill" + sfx, [])
-        st = self.__dict__.setdefault("pin_stats" + sfx, {"reused": 0, "new_pooled": 0, "spill": 0,
-                                                          "new_unpooled": 0})
-        for pin, arr in pool:
-            if arr.nbytes >= need and sys.getrefcount(arr) <= 3:   # pool tuple, loop variable, the call
-                st["reused"] += 1
-                return pin, arr, True
-        # sized to this step's rows plus slack (steps of one tenant are about the same size), not to
-        # the engine's full output capacity: pinning a buffer costs time in proportion to its size
-        if kind == "rows":
-            full = self.out_cap * OUT_REC_SIZE + self.ROW_HEADROOM
-        else:
-            from ..persistence.segments import max_block_bytes
-            full = max_block_bytes(self.out_cap) + self.ROW_HEADROOM
-        size = max(need, min(full, -(-(need + need // 4) // (1 << 20)) * (1 << 20)))
-        # never smaller than the largest pooled buffer: steps of a tenant that coalesces records vary
-        # in size, and pinning a fresh buffer for each new maximum costs milliseconds per step
-        if pool:
-            size = max(size, min(full, max(a.nbytes for _, a in pool)))
-        # results held by an overlapped tenant: in flight + store queue + storing, and -- with zero-copy
-        # columnar payloads -- the batches the store and the enriched-batch topic retain
-        if len(pool) < (self.PIN_POOL if kind == "rows" else self.PIN_POOL_BLOCKS):
-            pin = torch.empty(size, dtype=torch.uint8).pin_memory()
-            pool.append((pin, pin.numpy()))
-            st["new_pooled"] += 1
-            return pin, pool[-1][1], True
-        # every pooled buffer is retained downstream: hand out a spill buffer that must not be
-        # retained (the caller copies its rows), so a full pool costs a copy, not a pinned
-        # allocation per step
-        for pin, arr in spill:
-            if arr.nbytes >= need and sys.getrefcount(arr) <= 3:
-                st["spill"] += 1
-                return pin, arr, False
-        pin = torch.empty(size, dtype=torch.uint8).pin_memory()
-        if len(spill) < self.PIN_SPILL:
-            spill.append((pin, pin.numpy()))
-            st["spill"] += 1
-            return pin, spill[-1][1], False
-        st["new_unpooled"] += 1
-        return pin, pin.numpy(), False
-
+    ROW_HEADROOM = PinnedPool.HEADROOM
     PIN_POOL = 24
     PIN_POOL_BLOCKS = 64        # durable blocks: also held by the enriched-batch topic's retention window
     PIN_SPILL = 6
+
+    def _pinned_out(self, nbytes: int, kind: str = "rows"):
+        """(tensor, array, pooled): a pinned host buffer for a step's rows or its durable block
+        (``kind``), see :class:`PinnedPool`."""
+        return self._pins[kind].get(nbytes)
+
+    pin_stats = property(lambda self: self._pins["rows"].stats)
+    pin_stats_blocks = property(lambda self: self._pins["blocks"].stats)
 
     def collect(self, sel: int, raw_host: np.ndarray | None, from_device: bool = False) -> StepResult:
         part = self._collect_small(raw_host)
@@ -892,7 +879,7 @@ class GpuInboundEngine(EngineBase):
             self.carry_strs[cp][nb:nb + len(heap)].copy_(torch.from_numpy(heap))
         self.t["n_carry"][cp] = n + k
         self.t["n_carry_str"][cp] = nb + len(heap)
-        self.__dict__.pop("_carry_seen", None)
+        self._carry_seen = None
         self._sync_streams()
 
     # ------------------------------------------------------------------ overlapped framed steps
@@ -911,7 +898,6 @@ class GpuInboundEngine(EngineBase):
         The host never waits on a copy it just started, so PCIe stays busy in both directions."""
         if batch.lens is None or self.world > 1:
             return EngineBase.submit_framed(self, batch, now_ms, token, presence)
-        import warnings
         parts = getattr(batch, "parts", None)          # coalesced records: DMA'd back to back
         n, nl = batch.n_msgs, len(batch.lens)
         nb = batch.payload_bytes + _ALIGN if parts is not None else len(batch.payload)
@@ -926,7 +912,7 @@ class GpuInboundEngine(EngineBase):
                 done = EngineBase.drain_framed(self)
             else:
                 done = []
-            fp = self.__dict__.get("_fp")
+            fp = self._fp
             if fp is None:
                 fp = self._fp = _FramedSlots(self)
             b = fp.k % _FramedSlots.SLOTS
@@ -943,18 +929,18 @@ class GpuInboundEngine(EngineBase):
                 lsegs = [(_host_addr(part.lens), len(part.lens)) for part in parts if len(part.lens)]
             # the H2D of the zero-copy record straight from its pinned bytes, on the copy stream,
             # enqueued natively with the GIL held (see sw_memcpy_h2d_async)
-            L, hs = self.lib, ctypes.c_void_p(fp.h2d.cuda_stream)
-            _chk(L.sw_stream_wait_event(hs, ctypes.c_void_p(fp.ev_comp[b].cuda_event)))  # step k-3 read slot b last
+            L, hs = self.lib, fp.h2d.cuda_stream
+            _chk(L.sw_stream_wait_event(hs, fp.ev_comp[b].cuda_event), "sw_stream_wait_event")  # step k-3 read slot b last
             rd, ld = _ptr(dev_r), _ptr(dev_l)
             for st, src, m in segs:
-                _chk(L.sw_memcpy_h2d_async(ctypes.c_void_p(rd + st), ctypes.c_void_p(src), int(m), hs))
+                _chk(L.sw_memcpy_h2d_async(rd + st, src, int(m), hs), "sw_memcpy_h2d_async")
             if parts is not None:                          # the records' zero padding, after the last part
-                _chk(L.sw_memset_async(ctypes.c_void_p(rd + batch.payload_bytes), 0, _ALIGN, hs))
+                _chk(L.sw_memset_async(rd + batch.payload_bytes, 0, _ALIGN, hs), "sw_memset_async")
             lo = 0
             for src, m in lsegs:
-                _chk(L.sw_memcpy_h2d_async(ctypes.c_void_p(ld + lo), ctypes.c_void_p(src), int(m), hs))
+                _chk(L.sw_memcpy_h2d_async(ld + lo, src, int(m), hs), "sw_memcpy_h2d_async")
                 lo += m
-            _chk(L.sw_event_record(ctypes.c_void_p(fp.ev_h2d[b].cuda_event), hs))
+            _chk(L.sw_event_record(fp.ev_h2d[b].cuda_event, hs), "sw_event_record")
             t0 = self._ft("h2d_enqueue", t0)
             while len(fp.inflight) > 1 or (fp.inflight and fp.inflight[0].rows is not None):
                 done.append(self._framed_finish(fp.inflight.popleft()))      # batch k-2
@@ -968,8 +954,7 @@ class GpuInboundEngine(EngineBase):
                 self._block_meta(prev)              # before batch k is queued: no wait on it
                 t0 = self._ft("block_meta_k1", t0)
             cur = torch.cuda.current_stream(self.device)
-            _chk(self.lib.sw_stream_wait_event(ctypes.c_void_p(cur.cuda_stream),
-                                               ctypes.c_void_p(fp.ev_h2d[b].cuda_event)))
+            _chk(L.sw_stream_wait_event(cur.cuda_stream, fp.ev_h2d[b].cuda_event), "sw_stream_wait_event")
             self.frame_varint(dev_l, nl, n, dev_o, batch.payload_bytes)
             do_presence = self.presence_due(now_ms) if presence is None else presence
             self.step_async(dev_r[:nb], dev_o[:n + 1], n, now_ms, presence=do_presence, out_sel=b,
@@ -979,7 +964,7 @@ class GpuInboundEngine(EngineBase):
                 sub.bmeta, sub.now = self.encode_block_async(b), now_ms
             if self.world == 1:
                 self._snapshot_async(fp, b, sub)
-            _chk(self.lib.sw_event_record(ctypes.c_void_p(fp.ev_comp[b].cuda_event), ctypes.c_void_p(cur.cuda_stream)))
+            _chk(L.sw_event_record(fp.ev_comp[b].cuda_event, cur.cuda_stream), "sw_event_record")
             t0 = self._ft("step_enqueue", t0)
             if prev is not None:
                 self._framed_rows_start(prev)
@@ -1002,7 +987,7 @@ class GpuInboundEngine(EngineBase):
     def drain_framed(self) -> list:
         with self._lock:
             done = EngineBase.drain_framed(self) if getattr(self, "_lagged", None) is not None else []
-            fp = self.__dict__.get("_fp")
+            fp = self._fp
             while fp is not None and fp.inflight:
                 s = fp.inflight.popleft()
                 if s.small is None:
@@ -1015,8 +1000,7 @@ class GpuInboundEngine(EngineBase):
 
     @property
     def framed_pending(self) -> int:
-        fp = self.__dict__.get("_fp")
-        return EngineBase.framed_pending.fget(self) + (len(fp.inflight) if fp is not None else 0)
+        return EngineBase.framed_pending.fget(self) + (len(self._fp.inflight) if self._fp is not None else 0)
 
     # rejects per step read from the mapped snapshot; a step with more goes through _collect_small
     MAPPED_REJECTS = 1 << 18
@@ -1027,24 +1011,17 @@ class GpuInboundEngine(EngineBase):
         slot ``b``'s mapped host memory, so completing the step reads host memory only -- no
         synchronising device reads (each one gives the GIL up and waits to win it back from the
         tenant's other threads)."""
-        bufs = fp.__dict__.setdefault("snap", {})
         cap = min(self.cfg.rec_cap, self.MAPPED_REJECTS)
-        m = bufs.get(b)
+        m = fp.snap.get(b)
         if m is None:
-            m = bufs[b] = (HostBuffer(self.lib, 256), HostBuffer(self.lib, cap * EVENT_REC.itemsize),
-                           HostBuffer(self.lib, cap))
+            m = fp.snap[b] = (HostBuffer(self.lib, STEP_SNAPSHOT.itemsize),
+                              HostBuffer(self.lib, cap * EVENT_REC.itemsize), HostBuffer(self.lib, cap))
         snap, rej, st = m
-        st_ = self._stream()
-        sc = ctypes.c_void_p(_ptr(self.t["scalars"]))
-        meta = ctypes.c_void_p(sub.bmeta.data_ptr() if sub.bmeta is not None else 0)
-        rc = self.lib.sw_step_snapshot(sc, meta, None, None, 1, ctypes.c_void_p(snap.dev), st_)
-        if rc:
-            raise RuntimeError(f"sw_step_snapshot failed ({rc})")
-        rc = self.lib.sw_reject_pack(ctypes.c_void_p(_ptr(self.t["recs"])), ctypes.c_void_p(_ptr(self.t["rej_idx"])),
-                                     ctypes.c_void_p(_ptr(self.t["status"])), sc, cap, ctypes.c_void_p(rej.dev),
-                                     ctypes.c_void_p(st.dev), st_)
-        if rc:
-            raise RuntimeError(f"sw_reject_pack failed ({rc})")
+        stream, sc = self._stream(), _ptr(self.t["scalars"])
+        meta = sub.bmeta.data_ptr() if sub.bmeta is not None else None
+        _chk(self.lib.sw_step_snapshot(sc, meta, None, None, 1, snap.dev, stream), "sw_step_snapshot")
+        _chk(self.lib.sw_reject_pack(_ptr(self.t["recs"]), _ptr(self.t["rej_idx"]), _ptr(self.t["status"]), sc, cap,
+                                     rej.dev, st.dev, stream), "sw_reject_pack")
         sub.mapped = True
 
     def _collect_done(self, fp, s: "_Submitted") -> dict:
@@ -1053,108 +1030,66 @@ class GpuInboundEngine(EngineBase):
         if not s.mapped:
             return self._collect_small(host_view(s.batch))
         snap, rej, st = fp.snap[s.slot]
-        v = snap.view(np.uint32, 32)
-        n_rej = int(v[5])
+        v = snap.view(STEP_SNAPSHOT, 1)[0]
+        sc = v["scalars"]
+        n_rej = int(sc[SC_N_REJ])
         cap = min(self.cfg.rec_cap, self.MAPPED_REJECTS)
-        if int(v[1]) or n_rej > cap or s.bmeta is None:
+        if int(sc[SC_N_NEW_NAMES]) or n_rej > cap or s.bmeta is None:
             return self._collect_small(host_view(s.batch))
-        nb, err, first = (int(x) for x in snap.view(np.uint64, 11)[8:11])
-        if err or nb <= 0 or nb > self._seg_buffers(s.slot)[3]:
-            raise RuntimeError(f"durable block encoder failed (bytes={nb}, errors={err})")
-        s.bmeta = (nb, first)
+        s.bmeta = self._block_result(s.slot, v["block_bytes"], v["block_errors"], v["block_first_seq"])
         rows = rej.view(EVENT_REC, n_rej).copy() if n_rej else np.zeros(0, EVENT_REC)
         rst = st.view(np.uint8, n_rej).copy() if n_rej else np.zeros(0, np.uint8)
-        return dict(n_msgs=int(self.args.n_msgs), n_events=int(v[3]), n_persisted=int(v[7]), rejects=rows,
-                    reject_status=rst, new_names={}, first_seq=first, recheck=None)
+        return dict(n_msgs=int(self.args.n_msgs), n_events=int(sc[SC_N_WORK]), n_persisted=int(sc[SC_N_OUT]),
+                    rejects=rows, reject_status=rst, new_names={}, first_seq=s.bmeta[1], recheck=None)
+
+    def _block_result(self, slot: int, nb, err, first) -> tuple:
+        """(bytes, first store sequence) of slot ``slot``'s encoded block from the encoder's result
+        words; an encoder error, or a size outside the slot's buffer, raises."""
+        nb, err = int(nb), int(err)
+        if err or nb <= 0 or nb > self._seg_buffers(slot)[3]:
+            raise RuntimeError(f"durable block encoder failed (bytes={nb}, errors={err})")
+        return nb, int(first)
+
+    def _block_meta(self, s: "_Submitted"):
+        """Encoder result of completed step ``s`` (read while nothing newer is queued)."""
+        if s.bmeta is not None and not isinstance(s.bmeta, tuple):
+            s.bmeta = self._block_result(s.slot, *s.bmeta.cpu().numpy())
 
     def _framed_rows_start(self, s: "_Submitted"):
         """Start copying the rows (and the durable block) of completed step ``s`` to pinned host
         buffers."""
+        fp, hr = self._fp, self.ROW_HEADROOM
         if s.bmeta is not None:
-            self._framed_block_start(s)
+            self._block_meta(s)
+            s.bbuf = self._pinned_out(s.bmeta[0], kind="blocks")
+            s.bcopy = fp.copy_out(s.bbuf[0].data_ptr() + hr, _ptr(self.block_device(s.slot)), s.bmeta[0])
         nb = s.small["n_persisted"] * OUT_REC_SIZE
         s.rows = self._pinned_out(nb)
-        if not nb:
-            return
-        fp = self._fp
-        h = ctypes.c_uint64()
-        rc = 1 if fp.no_sdma else self.lib.sw_sdma_copy(ctypes.c_void_p(s.rows[0].data_ptr() + self.ROW_HEADROOM),
-                                                         ctypes.c_void_p(_ptr(self.out_dev[s.slot])), nb, 0,
-                                                         ctypes.byref(h))
-        if rc == 0:
-            s.sig = h.value
-            return
-        fp.no_sdma = True                       # no copy engine on this node: HIP runtime copy
-        with torch.cuda.stream(fp.d2h):
-            hr = self.ROW_HEADROOM
-            s.rows[0][hr:hr + nb].copy_(self.out_dev[s.slot][:nb], non_blocking=True)
-            s.ev = torch.cuda.Event()
-            s.ev.record(fp.d2h)
-
-    def _block_meta(self, s: "_Submitted"):
-        """Encoder result of completed step ``s`` (read while nothing newer is queued)."""
-        if s.bmeta is None or isinstance(s.bmeta, tuple):
-            return
-        nb, err, first = (int(x) for x in s.bmeta.cpu().numpy())
-        if err or nb <= 0 or nb > self._seg_buffers(s.slot)[3]:
-            raise RuntimeError(f"durable block encoder failed (bytes={nb}, errors={err})")
-        s.bmeta = (nb, first)
-
-    def _framed_block_start(self, s: "_Submitted"):
-        self._block_meta(s)
-        nb = s.bmeta[0]
-        s.bbuf = self._pinned_out(nb, kind="blocks")
-        dst = s.bbuf[0].data_ptr() + self.ROW_HEADROOM
-        fp = self._fp
-        h = ctypes.c_uint64()
-        rc = 1 if fp.no_sdma else self.lib.sw_sdma_copy(ctypes.c_void_p(dst), ctypes.c_void_p(_ptr(self.block_device(s.slot))),
-                                                         nb, 0, ctypes.byref(h))
-        if rc == 0:
-            s.bsig = h.value
-            return
-        fp.no_sdma = True
-        with torch.cuda.stream(fp.d2h):
-            hr = self.ROW_HEADROOM
-            s.bbuf[0][hr:hr + nb].copy_(self.block_device(s.slot)[:nb], non_blocking=True)
-            s.bev = torch.cuda.Event()
-            s.bev.record(fp.d2h)
-
-    def _framed_block_finish(self, s: "_Submitted", res: StepResult):
-        from ..persistence.segments import seal
-        if s.bsig is not None:
-            rc = self.lib.sw_sdma_wait(s.bsig)
-            s.bsig = None
-            if rc:
-                raise RuntimeError(f"sw_sdma_wait failed ({rc})")
-        elif s.bev is not None:
-            s.bev.synchronize()
-        nb, first = s.bmeta
-        hr = self.ROW_HEADROOM
-        pin, arr, pooled = s.bbuf
-        blk = arr[hr:hr + nb]
-        seal(blk, first, s.now, self.block_boot, self.rank, self.world)
-        if pooled:
-            res.block, res.block_frame = blk, (arr, hr)
-        else:
-            res.block = blk.copy()          # spill buffer: reused by the next step
-        s.bbuf = s.bmeta = None
+        if nb:
+            s.rcopy = fp.copy_out(s.rows[0].data_ptr() + hr, _ptr(self.out_dev[s.slot]), nb)
 
     def _framed_finish(self, s: "_Submitted"):
-        if s.sig is not None:
-            rc = self.lib.sw_sdma_wait(s.sig)
-            s.sig = None
-            if rc:
-                raise RuntimeError(f"sw_sdma_wait failed ({rc})")
-        elif s.ev is not None:
-            s.ev.synchronize()
+        if s.rcopy is not None:
+            s.rcopy.wait()
         nb = s.small["n_persisted"] * OUT_REC_SIZE
         hr = self.ROW_HEADROOM
         pin, arr, pooled = s.rows
         res = StepResult(out=arr[hr:hr + nb].view(OUT_REC), world=self.world, rank=self.rank,
                          frame_base=(arr, hr) if pooled else None, **s.small)
-        s.rows = None
+        s.rows = s.rcopy = None
         if s.bmeta is not None:
-            self._framed_block_finish(s, res)
+            from ..persistence.segments import seal
+            if s.bcopy is not None:
+                s.bcopy.wait()
+            nb, first = s.bmeta
+            pin, arr, pooled = s.bbuf
+            blk = arr[hr:hr + nb]
+            seal(blk, first, s.now, self.block_boot, self.rank, self.world)
+            if pooled:
+                res.block, res.block_frame = blk, (arr, hr)
+            else:
+                res.block = blk.copy()          # spill buffer: reused by the next step
+            s.bbuf = s.bmeta = s.bcopy = None
         return s.token, res
 
     # ------------------------------------------------------------------ durable blocks
@@ -1166,26 +1101,24 @@ class GpuInboundEngine(EngineBase):
     def _seg_buffers(self, slot: int):
         """(HBM block buffer, encoder state, max pages, capacity) of outbound slot ``slot``: each slot
         keeps its block until the copy engine has moved it to the host."""
-        segs = self.__dict__.setdefault("_segs", {})
-        s = segs.get(slot)
+        s = self._segs.get(slot)
         if s is None:
             from ..persistence.segments import PAGE_ROWS, SEG_ALIGN, max_block_bytes
             cap = max_block_bytes(self.out_cap, self.BLOCK_STRING_BYTES_PER_ROW * self.out_cap)
             if self.cfg.block_index:               # + the index trailer (swindex.h)
                 cap = -(-(cap + int(self.lib.sw_seg_index_max_bytes(self.out_cap))) // SEG_ALIGN) * SEG_ALIGN
             pages = -(-self.out_cap // PAGE_ROWS)
-            s = segs[slot] = (torch.empty(cap, dtype=torch.uint8, device=self.device),
-                              torch.zeros(pages + 8, dtype=torch.int64, device=self.device), pages, cap)
+            s = self._segs[slot] = (torch.empty(cap, dtype=torch.uint8, device=self.device),
+                                    torch.zeros(pages + SEG_ST_WORDS, dtype=torch.int64, device=self.device), pages, cap)
         return s
 
     SEG_AUX_SIZE = 32             # sizeof(SwSegAux), csrc/include/swseg.h
 
     def _aux_buffer(self, slot: int) -> torch.Tensor:
         """Encoder aux rows (SwSegAux) of outbound slot ``slot``, beside ``out_dev[slot]``."""
-        bufs = self.__dict__.setdefault("_aux_dev", {})
-        b = bufs.get(slot)
+        b = self._aux_dev.get(slot)
         if b is None:
-            b = bufs[slot] = torch.zeros(self.out_cap * self.SEG_AUX_SIZE, dtype=torch.uint8, device=self.device)
+            b = self._aux_dev[slot] = torch.zeros(self.out_cap * self.SEG_AUX_SIZE, dtype=torch.uint8, device=self.device)
         return b
 
     def encode_block_async(self, slot: int, snapshot: tuple | None = None) -> torch.Tensor:
@@ -1200,33 +1133,24 @@ class GpuInboundEngine(EngineBase):
         dev, state, pages, cap = self._seg_buffers(slot)
         a = self.args
         src = a.raw if self.world == 1 else (a.work_str or 0)
-        P = ctypes.c_void_p
+        rows, aux, cursor = _ptr(self.out_dev[slot]), _ptr(self._aux_buffer(slot)), _ptr(self.t["cursor"])
         if snapshot is not None:
-            rc = self.lib.sw_seg_encode_snap(P(_ptr(self.out_dev[slot])), P(_ptr(self._aux_buffer(slot))), P(src),
-                                             P(_ptr(self.t["cursor"])), P(_ptr(dev)), cap, P(_ptr(state)), pages,
-                                             *(P(x) for x in snapshot), self._stream())
-            if rc:
-                raise RuntimeError(f"sw_seg_encode_snap failed ({rc})")
+            _chk(self.lib.sw_seg_encode_snap(rows, aux, src, cursor, _ptr(dev), cap, _ptr(state), pages, *snapshot,
+                                             self._stream()), "sw_seg_encode_snap")
         else:
-            rc = self.lib.sw_seg_encode(P(_ptr(self.out_dev[slot])), P(_ptr(self._aux_buffer(slot))), P(src),
-                                        P(_ptr(self.t["cursor"])), P(_ptr(dev)), cap, P(_ptr(state)), pages,
-                                        self._stream())
-            if rc:
-                raise RuntimeError(f"sw_seg_encode failed ({rc})")
+            _chk(self.lib.sw_seg_encode(rows, aux, src, cursor, _ptr(dev), cap, _ptr(state), pages, self._stream()),
+                 "sw_seg_encode")
         if self.cfg.block_index:
             # the block's index trailer, built right behind the encoder on the same stream; its last
             # workgroup publishes the final block bytes (state, and the host snapshot when given)
             nk = self.ctx_key_spaces()
-            rc = self.lib.sw_seg_index(P(_ptr(self.out_dev[slot])), P(_ptr(self._aux_buffer(slot))), P(src),
-                                       P(_ptr(self.t["cursor"])), P(_ptr(self.store["alt"])), self.cfg.store_cap,
-                                       P(_ptr(self.t["asg_ctx"])), self.cfg.max_assignments, P(nk.ctypes.data),
-                                       P(_ptr(dev)), cap, P(_ptr(state)), pages,
-                                       P(snapshot[3] if snapshot is not None else 0),
-                                       P(_ptr(self._index_scratch(nk))), self.out_cap,
-                                       P(_ptr(self.ix_stamps) if self.ix_stamps is not None else 0), self._stream())
-            if rc:
-                raise RuntimeError(f"sw_seg_index failed ({rc})")
-        return state[pages + 1:pages + 4]
+            _chk(self.lib.sw_seg_index(rows, aux, src, cursor, _ptr(self.store["alt"]), self.cfg.store_cap,
+                                       _ptr(self.t["asg_ctx"]), self.cfg.max_assignments, nk.ctypes.data, _ptr(dev), cap,
+                                       _ptr(state), pages, snapshot[3] if snapshot is not None else None,
+                                       _ptr(self._index_scratch(nk)), self.out_cap,
+                                       _ptr(self.ix_stamps) if self.ix_stamps is not None else None, self._stream()),
+                 "sw_seg_index")
+        return state[pages + SEG_ST_BYTES:pages + SEG_ST_FIRST + 1]
 
     ix_stamps = None                # profiling: s_memrealtime stamps of the index build (see ix_probe)
 
@@ -1234,7 +1158,7 @@ class GpuInboundEngine(EngineBase):
         """Scratch of the block index build (one per engine: the builds run in stream order), sized for
         the context key spaces; zeroed when (re)allocated -- the build keeps it re-armed."""
         need = int(self.lib.sw_seg_index_scratch_words(self.out_cap, int(np.maximum(nk, 0).sum())))
-        t = self.__dict__.get("_ix_scratch")
+        t = self._ix_scratch
         if t is None or t.numel() < need:
             if t is not None:
                 self._sync_streams()            # the previous build may still read the old buffer
@@ -1250,19 +1174,15 @@ class GpuInboundEngine(EngineBase):
         and the compact copies of their payloads.  ``raw_dev`` / ``off_dev`` / ``n_msgs``: the batch
         whose local events this step processed.  Returns (counters, host buffer); the refs start at
         byte 0 of the host buffer, the copies at ``16 * rec_cap``."""
-        refs = self.__dict__.setdefault("_rej_refs", {})
-        bufs = refs.get(slot)
+        bufs = self._rej_refs.get(slot)
         cap = self.cfg.rec_cap
         if bufs is None:
-            bufs = refs[slot] = (torch.zeros(8, dtype=torch.int32, device=self.device),     # see k_reject_refs
+            bufs = self._rej_refs[slot] = (torch.zeros(8, dtype=torch.int32, device=self.device),     # see k_reject_refs
                                  HostBuffer(self.lib, 16 * cap + self.REJECT_BYTES))
         cnt, hb = bufs
-        rc = self.lib.sw_reject_refs(ctypes.byref(self.args), ctypes.c_void_p(_ptr(raw_dev)),
-                                     ctypes.c_void_p(_ptr(off_dev)), int(n_msgs), ctypes.c_void_p(_ptr(cnt)),
-                                     ctypes.c_void_p(hb.dev), cap, ctypes.c_void_p(hb.dev + 16 * cap),
-                                     self.REJECT_BYTES, self._stream())
-        if rc:
-            raise RuntimeError(f"sw_reject_refs failed ({rc})")
+        _chk(self.lib.sw_reject_refs(ctypes.byref(self.args), _ptr(raw_dev), _ptr(off_dev), int(n_msgs), _ptr(cnt),
+                                     hb.dev, cap, hb.dev + 16 * cap, self.REJECT_BYTES, self._stream()),
+             "sw_reject_refs")
         return bufs
 
     def reject_snapshot(self, slot: int, n_refs: int, n_bytes: int):
@@ -1287,9 +1207,7 @@ class GpuInboundEngine(EngineBase):
         with self._lock:
             meta = self.encode_block_async(slot)
             self._sync_streams()
-            nb, err, first = (int(x) for x in meta.cpu().numpy())
-            if err or nb <= 0 or nb > self._seg_buffers(slot)[3]:
-                raise RuntimeError(f"block encoder failed (bytes={nb}, errors={err})")
+            nb, first = self._block_result(slot, *meta.cpu().numpy())
             blk = self.block_device(slot)[:nb].cpu().numpy().copy()
         seal(blk, first, now_ms, boot, self.rank, self.world)
         return blk
@@ -1298,7 +1216,7 @@ class GpuInboundEngine(EngineBase):
         """Re-key carry: from the pipelined runner's last snapshot, else read (a sync)."""
         if self.world == 1:
             return 0
-        v = self.__dict__.get("_carry_seen")
+        v = self._carry_seen
         return v if v is not None else int(self.t["n_carry"].max().item())
 
     # ------------------------------------------------------------------ queries
@@ -1327,11 +1245,8 @@ class GpuInboundEngine(EngineBase):
             if getattr(self, "_sl_rows", None) is None or self._sl_rows.shape[0] < 2 * max(n_ids, 1):
                 self._sl_rows = torch.zeros((2 * max(n_ids, 64), 4), dtype=torch.int64, device=self.device)
                 self._sl_n = torch.zeros(1, dtype=torch.int32, device=self.device)
-            rc = self.lib.sw_state_lookup(ctypes.c_void_p(_ptr(self.t["ms"])), self.cfg.state_slots - 1, int(asg),
-                                          n_ids, ctypes.c_void_p(_ptr(self._sl_rows)), ctypes.c_void_p(_ptr(self._sl_n)),
-                                          ctypes.c_void_p(stream.cuda_stream))
-            if rc:
-                raise RuntimeError(f"sw_state_lookup failed ({rc})")
+            _chk(self.lib.sw_state_lookup(_ptr(self.t["ms"]), self.cfg.state_slots - 1, int(asg), n_ids,
+                                          _ptr(self._sl_rows), _ptr(self._sl_n), stream.cuda_stream), "sw_state_lookup")
             rows = self._sl_rows[:int(self._sl_n.item())].cpu().numpy().view(np.uint64)
             st = self.t["st"].view(-1, 4)[asg].cpu().numpy().view(ASG_STATE)[0]
             nids = np.unique(((rows[:, 0] - np.uint64(1)) & np.uint64(0xFFFFFFFF)) >> np.uint64(1)).astype(np.int64)
@@ -1380,14 +1295,10 @@ class GpuInboundEngine(EngineBase):
             self._q_n = torch.zeros(1, dtype=torch.int32, device=self.device)
         i64 = np.iinfo(np.int64)
         st = self.store
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self.lib.sw_store_filter(ctypes.c_void_p(_ptr(st["etype"])), ctypes.c_void_p(_ptr(st["asg"])),
-                                      ctypes.c_void_p(_ptr(st["date"])), n, int(event_type),
-                                      ctypes.c_void_p(_ptr(bits)), nbits, i64.min if start is None else int(start),
-                                      i64.max if end is None else int(end), ctypes.c_void_p(_ptr(self._q_rows)),
-                                      self._q_rows.numel(), ctypes.c_void_p(_ptr(self._q_n)), stream)
-        if rc:
-            raise RuntimeError(f"sw_store_filter failed ({rc})")
+        _chk(self.lib.sw_store_filter(_ptr(st["etype"]), _ptr(st["asg"]), _ptr(st["date"]), n, int(event_type),
+                                      _ptr(bits), nbits, i64.min if start is None else int(start),
+                                      i64.max if end is None else int(end), _ptr(self._q_rows), self._q_rows.numel(),
+                                      _ptr(self._q_n), self._stream()), "sw_store_filter")
         total = int(self._q_n.item())
         rows = self._q_rows[:total].long()
         seq = self._row_seq(rows, cur)
@@ -1437,19 +1348,14 @@ class GpuInboundEngine(EngineBase):
         c = self.cfg
         dev = torch.from_numpy(h.view(np.int64)).to(self.device)
         torch.cuda.current_stream(self.device).synchronize()
-        rc = self.lib.sw_ff_add(ctypes.c_void_p(_ptr(self.t["dd_ff"])), c.ff_buckets - 1, c.dedup_filter_gens, int(g),
-                                ctypes.c_void_p(_ptr(self.t["dd_ff_meta"])), ctypes.c_void_p(_ptr(dev)), len(h),
-                                self._stream())
-        if rc:
-            raise RuntimeError(f"sw_ff_add failed ({rc})")
+        _chk(self.lib.sw_ff_add(_ptr(self.t["dd_ff"]), c.ff_buckets - 1, c.dedup_filter_gens, int(g),
+                                _ptr(self.t["dd_ff_meta"]), _ptr(dev), len(h), self._stream()), "sw_ff_add")
         self._sync_streams()
 
     def _ff_clear(self, g: int):
         c = self.cfg
-        rc = self.lib.sw_ff_clear(ctypes.c_void_p(_ptr(self.t["dd_ff"])), c.ff_buckets - 1, c.dedup_filter_gens,
-                                  int(g), self._stream())
-        if rc:
-            raise RuntimeError(f"sw_ff_clear failed ({rc})")
+        _chk(self.lib.sw_ff_clear(_ptr(self.t["dd_ff"]), c.ff_buckets - 1, c.dedup_filter_gens, int(g), self._stream()),
+             "sw_ff_clear")
         self._sync_streams()
 
     def _ckpt_tables(self):
@@ -1592,7 +1498,6 @@ class PipelinedRunner:
         compute stream); the copy engine moves the compressed block to the sink's pinned buffer and
         the sink seals it, queues it to the durable store and publishes it.  ``submit(tag=...)``
         labels a batch; ``block_sink.committable()`` returns the labels whose blocks are durable."""
-        import os
         self.e = engine
         self.out_target = out_target
         dev = engine.device
@@ -1622,7 +1527,7 @@ class PipelinedRunner:
         # The multi-GPU exchange keeps depth 1 (its stall decisions read the carry of the last round).
         from collections import deque
         self.pending = deque()
-        self.copying = None          # sdma mode: (buffer, n_out) whose D2H copy is in flight
+        self.copying = None          # copy-engine modes: (slot, n_out, _CopyOut or None, token) in flight
         self.rounds = engine.world > 1 and os.environ.get("SW_PIPELINE_EXCHANGE", "1") != "0"
         self.produced = [False] * nb  # rounds mode: did the round in slot b process a batch
         self.depth = 1 if self.rounds else max(1, min(int(os.environ.get("SW_PIPELINE_DEPTH", 2)), nb - 1))
@@ -1633,7 +1538,7 @@ class PipelinedRunner:
             self.btag = [None] * nb       # caller tag of the batch whose block slot b holds
             self.bnow = [0] * nb
             self._prev_tag = None
-        self.bcopying = None              # (slot, signal, buffer, bytes, first_seq, now, tag)
+        self.bcopying = None              # (slot, _CopyOut, buffer, bytes, first_seq, now, tag)
         # SW_RUNNER_TRACE=1: host wall-clock per phase (bench attribution)
         self.trace = {} if os.environ.get("SW_RUNNER_TRACE") == "1" else None
         if self.trace is not None:      # device-side H2D and step time per slot (CUDA events)
@@ -1645,7 +1550,7 @@ class PipelinedRunner:
         self.rtag = [None] * nb
         # per-slot end-of-step snapshot in mapped host memory (k_step_snapshot): scalars, encoder
         # meta, reject counters -- read after the step's event, no copy calls
-        self.snap = [HostBuffer(engine.lib, 256) for _ in range(nb)]
+        self.snap = [HostBuffer(engine.lib, STEP_SNAPSHOT.itemsize) for _ in range(nb)]
         self.cpar = [0] * nb              # live carry parity when slot b's snapshot was taken
         # the slow path runs off the submit thread: the GPU writes the snapshot into mapped host
         # memory, routing runs on one worker thread in batch order; rejects_floor() tells callers the
@@ -1712,8 +1617,8 @@ class PipelinedRunner:
             if not self.produced[b]:
                 self.nout[b].zero_()
             else:
-                self.nout[b].copy_(self.e.t["scalars"][7:11])    # n_out on the device (stream-ordered)
-        rej_cnt = seg_meta = None
+                self.nout[b].copy_(self.e.t["scalars"][SC_N_OUT:SC_N_OUT + 4])    # n_out on the device (stream-ordered)
+        rej_cnt = None
         if self.on_rejects is not None:
             self.rtag[b] = None
             # in rounds mode the round processes the batch submitted by the previous call
@@ -1728,27 +1633,23 @@ class PipelinedRunner:
                 rej_cnt, _ = self.e.reject_refs_async(b, self.raw[done[0]], self.off[done[0]], done[1])
                 self.rtag[b] = done[2]
         nc = self.e.t.get("n_carry")
-        self.cpar[b] = getattr(self.e, "_carry_par", 0)
+        self.cpar[b] = self.e._carry_par
+        # (scalars, reject counters or null, carry counts or null, mapped host record)
+        snap_args = (self.e.t["scalars"].data_ptr(), None if rej_cnt is None else rej_cnt.data_ptr(),
+                     None if nc is None else nc.data_ptr(), self.snap[b].dev)
         snapped = False
         if self.block_sink is not None:
             done_tag = self._prev_tag if self.rounds else tag
             self._prev_tag = tag
             if self.produced[b]:
                 # the encoder's last workgroup writes the step snapshot too (one dispatch fewer)
-                seg_meta = self.e.encode_block_async(b, snapshot=(
-                    self.e.t["scalars"].data_ptr(), 0 if rej_cnt is None else rej_cnt.data_ptr(),
-                    0 if nc is None else nc.data_ptr(), self.snap[b].dev))
+                self.e.encode_block_async(b, snapshot=snap_args)
                 snapped = True
                 self.btag[b], self.bnow[b] = done_tag, self.e._step_now
         if not snapped:
-            rc = self.e.lib.sw_step_snapshot(ctypes.c_void_p(self.e.t["scalars"].data_ptr()),
-                                             ctypes.c_void_p(0 if seg_meta is None else seg_meta.data_ptr()),
-                                             ctypes.c_void_p(0 if rej_cnt is None else rej_cnt.data_ptr()),
-                                             ctypes.c_void_p(0 if nc is None else nc.data_ptr()),
-                                             int(self.produced[b]), ctypes.c_void_p(self.snap[b].dev),
-                                             ctypes.c_void_p(self.comp.cuda_stream))
-            if rc:
-                raise RuntimeError(f"sw_step_snapshot failed ({rc})")
+            sc, rej, carry, host = snap_args
+            _chk(self.e.lib.sw_step_snapshot(sc, None, rej, carry, int(self.produced[b]), host, self.comp.cuda_stream),
+                 "sw_step_snapshot")
         self.ev_comp[b].record(self.comp)
         if self.trace is not None:
             self.tev[b][2].record(self.comp)
@@ -1756,12 +1657,8 @@ class PipelinedRunner:
         if self.mode == "push" and self.deliver:
             with torch.cuda.stream(self.push):
                 self.push.wait_event(self.ev_comp[b])
-                rc = self.e.lib.sw_push_out(ctypes.c_void_p(_ptr(self.e.out_dev[b])),
-                                            ctypes.c_void_p(self.e.out_host[b].dev),
-                                            ctypes.c_void_p(_ptr(self.nout[b])), self.e.out_cap, self.push_blocks,
-                                            ctypes.c_void_p(self.push.cuda_stream))
-                if rc:
-                    raise RuntimeError(f"sw_push_out failed ({rc})")
+                _chk(self.e.lib.sw_push_out(_ptr(self.e.out_dev[b]), self.e.out_host[b].dev, _ptr(self.nout[b]),
+                                            self.e.out_cap, self.push_blocks, self.push.cuda_stream), "sw_push_out")
                 self.ev_push[b].record(self.push)
         self._t("enqueue", t_sub)
         self.pending.append(b)
@@ -1808,25 +1705,19 @@ class PipelinedRunner:
 
     def _finish_block(self):
         if self.bcopying is not None:
-            _, sig, buf, nb, first, now, tag = self.bcopying
+            _, copy, buf, nb, first, now, tag = self.bcopying
             self.bcopying = None
             t0 = time.perf_counter()
-            rc = self.e.lib.sw_sdma_wait(sig)
-            if rc:
-                raise RuntimeError(f"sw_sdma_wait failed ({rc})")
+            copy.wait()
             t0 = self._t("block_copy_wait", t0)
             self.block_sink.publish(buf, nb, first, now, tag)
             self._t("block_publish", t0)
 
     def _finish_rows(self):
         if self.copying is not None:
-            cb, cn, sig, tok = self.copying
-            if sig is not None:
-                rc = self.e.lib.sw_sdma_wait(sig)
-                if rc:
-                    raise RuntimeError(f"sw_sdma_wait failed ({rc})")
-            else:
-                self.ev_push[cb].synchronize()
+            cb, cn, copy, tok = self.copying
+            if copy is not None:
+                copy.wait()
             self._deliver(cb, cn, tok)
             self.copying = None
 
@@ -1852,61 +1743,45 @@ class PipelinedRunner:
                 ev[1].elapsed_time(ev[2]) / 1000
         if self.mode == "push" and self.deliver:
             self.ev_push[pb].synchronize()
-        snap = self.snap[pb].view(np.uint32, 32)
-        n_out = int(snap[7]) if self.produced[pb] else 0
+        snap = self.snap[pb].view(STEP_SNAPSHOT, 1)[0]
+        n_out = int(snap["scalars"][SC_N_OUT]) if self.produced[pb] else 0
         if self.e.world > 1:
             # re-key carry after this round: the parity its partition spilled into
-            self.e._carry_seen = int(snap[22 + self.cpar[pb]])
+            self.e._carry_seen = int(snap["n_carry"][self.cpar[pb]])
         if self.on_rejects is not None and self.produced[pb] and self.rtag[pb] is not None:
-            n_rej = int(snap[24])
+            n_rej = int(snap["rej_refs"])
             if n_rej:
-                self._rejects_async(pb, n_rej, int(snap[25]))
+                self._rejects_async(pb, n_rej, int(snap["rej_bytes"]))
                 t0 = self._t("rejects_enqueue", t0)
         if self.mode not in ("sdma", "hsa"):
             self._deliver(pb, n_out)
             return
         self._finish_copy()
         t0 = self._t("finish_copy", t0)
+        e = self.e
         if self.block_sink is not None and self.produced[pb]:
-            nb, err, first = (int(x) for x in self.snap[pb].view(np.uint64, 11)[8:11])
-            if err or nb <= 0 or nb > self.e._seg_buffers(pb)[3]:
-                raise RuntimeError(f"durable block encoder failed (bytes={nb}, errors={err})")
+            nb, first = e._block_result(pb, snap["block_bytes"], snap["block_errors"], snap["block_first_seq"])
             dst, buf = self.block_sink.target(nb)
-            h = ctypes.c_uint64()
-            rc = self.e.lib.sw_sdma_copy(ctypes.c_void_p(dst), ctypes.c_void_p(_ptr(self.e.block_device(pb))), nb,
-                                         self.sdma_engine, ctypes.byref(h))
-            if rc:
-                raise RuntimeError(f"sw_sdma_copy of the durable block failed ({rc})")
-            self.bcopying = (pb, h.value, buf, nb, first, self.bnow[pb], self.btag[pb])
+            copy = _CopyOut(e.lib, dst, _ptr(e.block_device(pb)), nb, self.sdma_engine)
+            if copy.engine_rc:
+                raise RuntimeError(f"sw_sdma_copy of the durable block failed ({copy.engine_rc})")
+            self.bcopying = (pb, copy, buf, nb, first, self.bnow[pb], self.btag[pb])
             t0 = self._t("block_copy_start", t0)
-        dst, tok = self._dest(pb, n_out) if self.deliver and n_out else (None, None)
-        if self.mode == "hsa":
-            sig = None
-            if self.deliver and n_out:
-                h = ctypes.c_uint64()
-                rc = self.e.lib.sw_sdma_copy(ctypes.c_void_p(dst),
-                                             ctypes.c_void_p(_ptr(self.e.out_dev[pb])), n_out * OUT_REC.itemsize,
-                                             self.sdma_engine, ctypes.byref(h))
-                if rc == 0:
-                    sig = h.value
-                else:
-                    # copy engine unavailable on this node: degrade to the HIP runtime path (loudly)
-                    import warnings
-                    warnings.warn(f"sw_sdma_copy failed ({rc}); falling back to hipMemcpyAsync outbound")
-                    self.mode = "sdma"
-            if self.mode == "hsa":
-                self.copying = (pb, n_out, sig, tok)
-                if sig is None:
-                    self._finish_rows()
-                return
+        copy = tok = None
         if self.deliver and n_out:
-            rc = self.e.lib.sw_copy_d2h(ctypes.c_void_p(dst),
-                                        ctypes.c_void_p(_ptr(self.e.out_dev[pb])), n_out * OUT_REC.itemsize,
-                                        ctypes.c_void_p(self.push.cuda_stream))
-            if rc:
-                raise RuntimeError(f"sw_copy_d2h failed ({rc})")
-        self.ev_push[pb].record(self.push)
-        self.copying = (pb, n_out, None, tok)
+            dst, tok = self._dest(pb, n_out)
+            copy = _CopyOut(e.lib, dst, _ptr(e.out_dev[pb]), n_out * OUT_REC.itemsize, self.sdma_engine, self.push,
+                            self.ev_push[pb], use_engine=self.mode == "hsa")
+            if copy.engine_rc:
+                # copy engine unavailable on this node: degrade to the HIP runtime path (loudly)
+                import warnings
+                warnings.warn(f"sw_sdma_copy failed ({copy.engine_rc}); falling back to hipMemcpyAsync outbound")
+                self.mode = "sdma"
+        elif self.mode == "sdma":
+            self.ev_push[pb].record(self.push)          # submit orders the ring's reuse behind it
+        self.copying = (pb, n_out, copy, tok)
+        if self.mode == "hsa" and copy is None:
+            self._finish_rows()
 
     def flush(self):
         if self.rounds and self.e.exchange_pending:
@@ -1921,5 +1796,5 @@ class PipelinedRunner:
         self.rejects_floor()
 
     def outbound(self, b: int) -> np.ndarray:
-        n = int(self.snap[b].view(np.uint32, 32)[7]) if self.produced[b] else 0
+        n = int(self.snap[b].view(STEP_SNAPSHOT, 1)["scalars"][0, SC_N_OUT]) if self.produced[b] else 0
         return self.e.out_host[b].view(OUT_REC, n)

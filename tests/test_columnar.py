@@ -5,6 +5,8 @@ from __future__ import annotations
 
 import ctypes
 import re
+
+import numpy as np
 from pathlib import Path
 
 from sitewhere_amd.ops import engine_abi
@@ -29,3 +31,42 @@ def test_engine_args_fields_match_header():
     assert len(fields) == 132
     assert fields == engine_abi.FIELDS
     assert ctypes.sizeof(engine_abi.SwEngineArgs) == 8 * len(fields)
+
+
+def test_step_snapshot_matches_header():
+    """STEP_SNAPSHOT and the SC_* word indices (sitewhere_amd/models/columnar.py) against
+    SwStepSnapshot and the SW_SC_* enum: same names, offsets, sizes and values."""
+    from sitewhere_amd.models import columnar as col
+    text = re.sub(r"//[^\n]*", "", HEADER.read_text())
+    enum, nxt = {}, 0
+    for item in re.search(r"enum \{\s*(SW_SC_N_RECS.*?)\};", text, re.S).group(1).split(","):
+        if item.strip():
+            m = re.fullmatch(r"(SW_SC_\w+)(?:\s*=\s*(\d+))?", item.strip())
+            assert m, f"unparsed enumerator: {item!r}"
+            nxt = int(m.group(2)) if m.group(2) else nxt
+            enum[m.group(1)] = nxt
+            nxt += 1
+    words = enum.pop("SW_SC_WORDS")
+    assert words == col.SC_WORDS == 16
+    assert enum == {"SW_" + k: getattr(col, k) for k in dir(col) if k.startswith("SC_N_") or k == "SC_OVERFLOW"}
+    assert [k[6:].lower() for k in sorted(enum, key=enum.get)] == list(col.SC_NAMES)
+    assert sorted(enum.values()) == list(range(len(col.SC_NAMES)))
+    body = re.search(r"typedef struct SwStepSnapshot \{(.*?)\} SwStepSnapshot;", text, re.S).group(1)
+    fields, off = [], 0
+    for decl in body.split(";"):
+        if not decl.strip():
+            continue
+        ctype, names = decl.split(None, 1)
+        size = {"uint32_t": 4, "uint64_t": 8}[ctype]
+        for name in names.split(","):
+            m = re.fullmatch(r"(\w+)(?:\[(\w+)\])?", name.strip())
+            assert m, f"unparsed declaration in SwStepSnapshot: {decl!r}"
+            n = 1 if m.group(2) is None else words if m.group(2) == "SW_SC_WORDS" else int(m.group(2))
+            off = -(-off // size) * size
+            fields.append((m.group(1), off, size, n))
+            off += size * n
+    dt = col.STEP_SNAPSHOT
+    got = [(k, dt.fields[k][1], dt.fields[k][0].base.itemsize, int(np.prod(dt.fields[k][0].shape, dtype=int)))
+           for k in dt.names]
+    assert got == fields
+    assert dt.itemsize == off == 128

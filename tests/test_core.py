@@ -546,18 +546,21 @@ def test_zero_copy_columnar_frame_matches_encoded_batch():
 
 
 def test_pinned_row_pool_sizes_recycles_and_spills(monkeypatch):
-    """The engine's pinned row buffers (GpuInboundEngine._pinned_out): sized to the step's rows plus
-    slack (not the full output capacity), reused once nothing references them, and -- when every
-    pooled buffer is held downstream (zero-copy payloads retained by the store / topic) -- a small
-    set of recycled spill buffers marked not-retainable instead of a pinned allocation per step.
-    Pinning itself is stubbed: the pool logic is host code."""
+    """The engine's pinned row buffers (PinnedPool, behind GpuInboundEngine._pinned_out): sized to the
+    step's rows plus slack (not the full output capacity), reused once nothing references them, and
+    -- when every pooled buffer is held downstream (zero-copy payloads retained by the store /
+    topic) -- a small set of recycled spill buffers marked not-retainable instead of a pinned
+    allocation per step.  Pinning itself is stubbed: the pool logic is host code."""
+    from types import SimpleNamespace
+
     import torch
 
-    from sitewhere_amd.pipeline.gpu_engine import GpuInboundEngine
+    from sitewhere_amd.pipeline.pinned_pool import PinnedPool
     monkeypatch.setattr(torch.Tensor, "pin_memory", lambda self: self)
-    eng = object.__new__(GpuInboundEngine)
-    eng.out_cap = 1 << 20                                     # 32 MB of rows at full capacity
-    eng.PIN_POOL, eng.PIN_SPILL = 3, 2
+    out_cap = 1 << 20                                         # 32 MB of rows at full capacity
+    pool = PinnedPool(out_cap * 32, limit=3, spill=2)
+    eng = SimpleNamespace(out_cap=out_cap, ROW_HEADROOM=PinnedPool.HEADROOM, pin_stats=pool.stats,
+                          _pinned_out=pool.get)               # the names the engine gives the pool
     need = 65536 * 32
     pin, arr, pooled = eng._pinned_out(need)
     assert pooled and need + eng.ROW_HEADROOM <= arr.nbytes <= 4 << 20

@@ -48,6 +48,8 @@ def test_abi_sizes_match():
     assert [s["reg_slot"], s["asg_state"], s["ms_slot"]] == [32, 32, 32]
     from sitewhere_amd.models.columnar import WIRE_REC
     assert s["wire_rec"] == WIRE_REC.itemsize == 64
+    from sitewhere_amd.models.columnar import STEP_SNAPSHOT
+    assert s["step_snapshot"] == STEP_SNAPSHOT.itemsize == 128
 
 
 def test_hand_batch_parity():
@@ -267,3 +269,120 @@ def test_overlapped_framed_steps_match_sync_oracle():
         assert rg.n_msgs == rc.n_msgs and rg.n_events == rc.n_events
     assert g.stats_dict() == c.stats_dict()
     assert sum(len(r.rejects) for _, r in got) > 0                # unregistered devices were rejected
+
+
+class _StubSink:
+    """A durable-block sink over mapped pinned host memory: ``target`` hands out a buffer the copy
+    engine writes, ``publish`` seals the block and keeps a copy of it."""
+
+    def __init__(self, lib, boot):
+        self.lib, self.boot, self.published = lib, boot, []
+
+    def target(self, nbytes):
+        from sitewhere_amd.pipeline.gpu_engine import HostBuffer
+        hb = HostBuffer(self.lib, nbytes)
+        return hb.host, hb
+
+    def publish(self, buf, nbytes, first_seq, now, tag):
+        from sitewhere_amd.persistence import segments as sg
+        blk = buf.view(np.uint8, nbytes).copy()
+        sg.seal(blk, first_seq, now, self.boot, 0, 1)
+        self.published.append((tag, int(first_seq), blk))
+
+
+@pytest.mark.parametrize("block_index", [False, True], ids=["plain", "indexed"])
+def test_pipelined_runner_block_sink_and_rejects_match_oracle(block_index):
+    """The runner as the benchmark drives it: a durable-block sink (the encoder's last workgroup
+    writes the step snapshot; with ``block_index`` the index build's patches the block bytes) and a
+    reject callback, five batches over the three-slot ring.  Every step's block, first sequence, tag
+    and routed rejects equal the CPU oracle's synchronous step of the same batch."""
+    from sitewhere_amd.persistence import segments as sg
+    from sitewhere_amd.pipeline import routing
+    from tests.test_gpu_index import _strip_trailer
+    from tests.test_gpu_segments import _decoded_equal
+    g, c = pair(block_index=block_index)
+    sink = _StubSink(g.lib, boot=0xabc)
+    rejects = {}
+    runner = PipelinedRunner(g, max_raw_bytes=1 << 20, deliver_outbound=False, block_sink=sink,
+                             on_rejects=lambda tag, refs, comp: rejects.__setitem__(tag, (refs.copy(), comp.copy())))
+    parts = (8, 4, 8, 2)
+    want, total = [], 0
+    for k in range(5):
+        raw, offs = fleet_batch(2000, seed=300 + k)
+        rh = torch.from_numpy(raw).pin_memory()
+        oh = torch.from_numpy(offs.view(np.int32)).pin_memory()
+        runner.submit(rh, oh, len(offs) - 1, now_ms=NOW + k, tag=k)
+        rc = c.step(raw, offs, NOW + k, presence=False)
+        host = routing.route_rejects(raw, offs, rc.rejects["aux_off"], rc.reject_status, "gpu-inbound", parts)
+        want.append((rc.first_seq, c.encode_block(NOW + k, rc, boot=0xabc), host))
+        total += rc.n_persisted
+    runner.flush()
+    assert runner.delivered == total > 0
+    assert [t for t, _, _ in sink.published] == list(range(5))
+    gi = {i: h for h, i in g.intern_table().items()}
+    ci = {i: h for h, i in c.intern_table().items()}
+    to_hash = lambda ids, inv: [inv.get(int(i), -1) if i != 0xFFFF else -1 for i in ids]  # noqa: E731
+    for k, ((_, first, bg), (cfirst, bc, host)) in enumerate(zip(sink.published, want)):
+        assert first == cfirst, f"step {k}"
+        assert sg.verify(bg) == 0
+        cg, cc = sg.decode_block(bg), sg.decode_block(bc)
+        _decoded_equal(cg, cc, f"step {k}")
+        assert to_hash(cg["name"], gi) == to_hash(cc["name"], ci), f"step {k}: names differ"
+        assert cg["header"]["first_seq"] == cfirst
+        if block_index:
+            assert np.array_equal(sg.index_block(_strip_trailer(bg), g.ctx_table()), bg), f"step {k}: trailer"
+        if k not in rejects:                    # no callback: the step had nothing to route
+            assert len(host) == 0, f"step {k}"
+            continue
+        gpu = routing.route_refs(rejects[k][1], rejects[k][0], 0, "gpu-inbound", parts)
+        assert len(gpu) > 0 and gpu.payloads == host.payloads, f"step {k}"
+        gk = sorted((q, p, bytes(kh), bytes(vh)) for q, p, kh, ko, vh, vo in gpu.groups())
+        hk = sorted((q, p, bytes(kh), bytes(vh)) for q, p, kh, ko, vh, vo in host.groups())
+        assert gk == hk, f"step {k}"
+    assert len(rejects) > 0
+    assert g.stats_dict() == c.stats_dict()
+
+
+def test_step_snapshot_kernel_writes_the_named_layout():
+    """``k_step_snapshot`` on its own, after a synchronous step, its block encode and its reject
+    snapshot: every word of the record it writes into mapped host memory against the device values
+    it copies; without a produced step only the carry words are set."""
+    from sitewhere_amd.models.columnar import SC_NAMES, SEG_ST_BYTES, SEG_ST_FIRST, STEP_SNAPSHOT
+    from sitewhere_amd.pipeline.gpu_engine import HostBuffer
+    g, _ = pair()
+    raw, offs = hand_batch()
+    g.step(raw, offs, NOW, presence=False)
+    slot = g._last_sel
+    meta = g.encode_block_async(slot)
+    cnt, _ = g.reject_refs_async(slot, g._stg[2], g._stg[3], len(offs) - 1)
+    carry = torch.tensor([7, 9], dtype=torch.int32, device=g.device)      # one rank keeps no carry: stand-ins
+    hb = HostBuffer(g.lib, 256)
+    stream = torch.cuda.current_stream(g.device)
+
+    def snapshot(produced):
+        hb.view(np.uint8, 256)[:] = 0
+        hb.view(np.uint8, STEP_SNAPSHOT.fields["pad"][1])[:] = 0xA5       # every word the kernel owns
+        rc =g.lib.sw_step_snapshot(g.t["scalars"].data_ptr(), meta.data_ptr(), cnt.data_ptr(), carry.data_ptr(),
+                                    produced, hb.dev, stream.cuda_stream)
+        assert rc == 0
+        stream.synchronize()
+        return hb.view(STEP_SNAPSHOT, 1)[0].copy()
+
+    s = snapshot(1)
+    sc = g.scalars()
+    assert sc["n_out"] > 0 and sc["n_rej"] > 0
+    words = g.t["scalars"][:16].cpu().numpy().view(np.uint32)
+    assert s["scalars"].tolist() == words.tolist()
+    assert {n: int(s["scalars"][i]) for i, n in enumerate(SC_NAMES)} == sc
+    _, state, pages, cap = g._seg_buffers(slot)
+    st = state[pages + SEG_ST_BYTES:pages + SEG_ST_FIRST + 1].cpu().numpy().view(np.uint64)
+    assert [int(s["block_bytes"]), int(s["block_errors"]), int(s["block_first_seq"])] == [int(x) for x in st]
+    assert 0 < int(s["block_bytes"]) <= cap and int(s["block_errors"]) == 0
+    counters = cnt.cpu().numpy().view(np.uint32)
+    assert [int(s["rej_refs"]), int(s["rej_bytes"])] == [int(counters[0]), int(counters[1])]
+    assert int(s["rej_refs"]) > 0
+    assert s["n_carry"].tolist() == [7, 9]
+    s0 = snapshot(0)
+    assert s0["n_carry"].tolist() == [7, 9]
+    s0["n_carry"] = 0
+    assert s0.tobytes() == bytes(STEP_SNAPSHOT.itemsize)

@@ -21,7 +21,7 @@ def _encode_gpu(rows, recs, spans, raw, c0=0, seed=0):
     the encoder aux rows built from them by ``k_seg_aux`` (the persist kernel's per-row write)."""
     import torch
     from sitewhere_amd._native import gpu
-    from sitewhere_amd.models.columnar import EVENT_REC, OUT_REC, STR_REF
+    from sitewhere_amd.models.columnar import EVENT_REC, OUT_REC, SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, STR_REF
     from sitewhere_amd.persistence.segments import PAGE_ROWS, max_block_bytes, max_string_bytes
     lib = gpu()
     n = len(rows)
@@ -50,7 +50,7 @@ def _encode_gpu(rows, recs, spans, raw, c0=0, seed=0):
     bcap = max_block_bytes(max_rows, max_string_bytes(max_rows, len(raw)))
     pages = -(-max_rows // PAGE_ROWS)
     blk = torch.zeros(bcap, dtype=torch.uint8, device=d)
-    state = torch.zeros(pages + 8, dtype=torch.int64, device=d)
+    state = torch.zeros(pages + SEG_ST_WORDS, dtype=torch.int64, device=d)
     s = torch.cuda.current_stream(d)
     P = ctypes.c_void_p
     # encoder aux rows from the records (what the engine's persist kernel writes beside each row)
@@ -63,7 +63,7 @@ def _encode_gpu(rows, recs, spans, raw, c0=0, seed=0):
                            P(blk.data_ptr()), bcap, P(state.data_ptr()), pages, P(s.cuda_stream))
     assert rc == 0
     s.synchronize()
-    nb, err, first = (int(x) for x in state[pages + 1:pages + 4].cpu().numpy())
+    nb, err, first = (int(x) for x in state[pages + SEG_ST_BYTES:pages + SEG_ST_FIRST + 1].cpu().numpy())
     assert err == 0 and 0 < nb <= bcap, (nb, err)
     assert first == c0
     return blk[:nb].cpu().numpy()
