@@ -1711,6 +1711,178 @@ __global__ __launch_bounds__(BLK) void k_store_filter(const uint8_t* __restrict_
   }
 }
 
+// ============================================================================ hot-store series
+// Measurement series in time buckets straight from the ring (sw_store_series): measurement rows of
+// an assignment set and a name set in [start, end] are reduced into cells (name index, (date - start)
+// / bucket_ms) -- count, sum, min, max and the first / last row by (date, event id) -- and only the
+// cells leave the GPU.  Nothing here is a floating-point atomic and no order depends on the
+// scheduler, so the same ring gives the same bytes:
+//   k_series_count   each wave owns a fixed run of ring rows and writes its match count
+//   k_series_emit    the same test again; (cell, row) pairs compacted in ring-row order at the prefix
+//                    of those counts (prologue reduce: no flags, no waiting)
+//   radix sort       stable, by cell: a cell's rows stay in ring-row order
+//   k_series_reduce  fixed 256-pair tiles: the first thread of each run of a cell folds the run left
+//                    to right from LDS; a run inside the tile is the whole cell and is written, the
+//                    runs touching the tile's ends go to the tile's two carry slots
+//   k_series_carry   carry slots are in cell order: the first slot of a cell folds the following
+//                    slots of that cell in tile order and writes the cell
+// The 1-byte type column is the only one read for every row; name, value and the bucket division
+// only for rows that pass the type, assignment and date tests.
+#define SERIES_NO_CELL 0xFFFFFFFFu
+
+// The row's cell; -1: no match; -2: a match whose value is NaN (counted, in no cell).
+__device__ __forceinline__ int32_t series_cell(const SwSeriesQuery& q, const uint64_t* names, int64_t r) {
+  if (r >= q.n_rows || q.etype[r] != (uint8_t)SW_EV_MEASUREMENT) return -1;
+  const int32_t a = q.asg[r];
+  if (a < 0 || a >= q.n_asg || !((q.bits[a >> 5] >> (a & 31)) & 1u)) return -1;
+  const int64_t d = q.date[r];
+  if (d < q.start || d > q.end) return -1;
+  const uint64_t h = q.name[r];
+  int32_t i = 0;
+  while (i < (int32_t)q.n_names && names[i] != h) ++i;
+  if (i == (int32_t)q.n_names) return -1;
+  const double v = q.v0[r];
+  if (v != v) return -2;
+  return i * (int32_t)q.n_buckets + (int32_t)((d - q.start) / q.bucket_ms);
+}
+
+__device__ __forceinline__ void series_names_to_lds(const SwSeriesQuery& q, uint64_t* names) {
+  if (threadIdx.x < (uint32_t)q.n_names) names[threadIdx.x] = q.names[threadIdx.x];
+  __syncthreads();
+}
+
+// counters: [0] matches, [1] NaN rows (integer atomics: totals, the same in any order).
+__global__ __launch_bounds__(BLK) void k_series_count(const SwSeriesQuery q, uint32_t* __restrict__ sums,
+                                                      uint32_t* __restrict__ counters) {
+  __shared__ uint64_t names[SW_SERIES_MAX_NAMES];
+  series_names_to_lds(q, names);
+  const int64_t chunk = (int64_t)BID * WAVES + (threadIdx.x >> 6);
+  int64_t r = chunk * q.rounds * 64 + lane_id();
+  uint32_t cnt = 0, nan = 0;
+  for (int64_t it = 0; it < q.rounds; ++it, r += 64) {
+    const int32_t c = series_cell(q, names, r);
+    cnt += (uint32_t)__popcll(__ballot(c >= 0));
+    nan += (uint32_t)__popcll(__ballot(c == -2));
+  }
+  if (lane_id() == 0) {
+    sums[chunk] = cnt;
+    if (cnt) atomicAdd(&counters[0], cnt);
+    if (nan) atomicAdd(&counters[1], nan);
+  }
+}
+
+__global__ __launch_bounds__(BLK) void k_series_emit(const SwSeriesQuery q, const uint32_t* __restrict__ sums,
+                                                     uint32_t* __restrict__ keys, uint32_t* __restrict__ rows,
+                                                     int64_t cap) {
+  __shared__ uint64_t names[SW_SERIES_MAX_NAMES];
+  __shared__ uint32_t red[WAVES + 1];
+  series_names_to_lds(q, names);
+  const uint32_t wid = threadIdx.x >> 6;
+  const int64_t chunk = (int64_t)BID * WAVES + wid;
+  uint32_t before = 0, mine = 0;                 // matches of this workgroup's waves before this one, and all
+  for (uint32_t w = 0; w < WAVES; ++w) {
+    const uint32_t c = sums[chunk - wid + w];
+    before += w < wid ? c : 0u;
+    mine += c;
+  }
+  if (mine == 0) return;                         // the whole workgroup: no barrier is left waiting
+  uint32_t base = block_sum_prefix(sums, (int64_t)BID * WAVES, red) + before;
+  if (sums[chunk] == 0) return;
+  int64_t r = chunk * q.rounds * 64 + lane_id();
+  for (int64_t it = 0; it < q.rounds; ++it, r += 64) {
+    const int32_t c = series_cell(q, names, r);
+    const ull mask = __ballot(c >= 0);
+    if (c >= 0) {
+      const int64_t pos = (int64_t)base + __popcll(mask & lanemask_lt());
+      if (pos < cap) { keys[pos] = (uint32_t)c; rows[pos] = (uint32_t)r; }
+    }
+    base += (uint32_t)__popcll(mask);
+  }
+}
+
+// b follows a in the fold order (ring-row order within a cell).
+__device__ __forceinline__ void series_merge(SwSeriesCell& a, const SwSeriesCell& b) {
+  a.count += b.count;
+  a.sum += b.sum;
+  if (b.min < a.min) a.min = b.min;
+  if (b.max > a.max) a.max = b.max;
+  if (b.first_date < a.first_date || (b.first_date == a.first_date && b.first_id < a.first_id)) {
+    a.first = b.first; a.first_date = b.first_date; a.first_id = b.first_id;
+  }
+  if (b.last_date > a.last_date || (b.last_date == a.last_date && b.last_id > a.last_id)) {
+    a.last = b.last; a.last_date = b.last_date; a.last_id = b.last_id;
+  }
+}
+
+__global__ __launch_bounds__(BLK) void k_series_reduce(const SwSeriesQuery q, const uint32_t* __restrict__ keys,
+                                                       const uint32_t* __restrict__ rows,
+                                                       const uint32_t* __restrict__ n_ptr, int64_t n_cells,
+                                                       SwSeriesCell* __restrict__ cells, SwSeriesCell* __restrict__ carry,
+                                                       uint32_t* __restrict__ ckey) {
+  __shared__ uint32_t sk[BLK];
+  __shared__ double sv[BLK];
+  __shared__ int64_t sd[BLK], ss[BLK];
+  const int64_t n = *n_ptr, base = (int64_t)BID * BLK;
+  if (base >= n) return;
+  const uint32_t t = threadIdx.x, m = (uint32_t)(n - base < BLK ? n - base : BLK);
+  if (t < m) {
+    const int64_t row = rows[base + t];
+    sk[t] = keys[base + t];
+    sv[t] = q.v0[row];
+    sd[t] = q.date[row];
+    ss[t] = q.seq0 + (row >= q.head ? row - q.head : row - q.head + q.n_rows);
+  }
+  __syncthreads();
+  if (t >= m) return;
+  const uint32_t k = sk[t];
+  if (t > 0 && sk[t - 1] == k) return;
+  SwSeriesCell c;
+  c.count = 1;
+  c.sum = c.min = c.max = c.first = c.last = sv[t];
+  c.first_date = c.last_date = sd[t];
+  c.first_id = c.last_id = ss[t];
+  uint32_t j = t + 1;
+  for (; j < m && sk[j] == k; ++j) {
+    const double v = sv[j];
+    const int64_t d = sd[j], s = ss[j];
+    c.count += 1;
+    c.sum += v;
+    if (v < c.min) c.min = v;
+    if (v > c.max) c.max = v;
+    if (d < c.first_date || (d == c.first_date && s < c.first_id)) { c.first = v; c.first_date = d; c.first_id = s; }
+    if (d > c.last_date || (d == c.last_date && s > c.last_id)) { c.last = v; c.last_date = d; c.last_id = s; }
+  }
+  if (t > 0 && j < m) {
+    if ((int64_t)k < n_cells) cells[k] = c;
+    return;
+  }
+  // a run touching the tile's ends: slot 0 holds the run of the first pair, slot 1 the run of the last
+  // pair when that is another run
+  const int64_t slot = 2 * (int64_t)BID + (t > 0 ? 1 : 0);
+  carry[slot] = c;
+  ckey[slot] = k;
+  if (t == 0 && j == m) ckey[slot + 1] = SERIES_NO_CELL;
+}
+
+__global__ __launch_bounds__(BLK) void k_series_carry(const SwSeriesCell* __restrict__ carry,
+                                                      const uint32_t* __restrict__ ckey, int64_t n_slots, int64_t n_cells,
+                                                      SwSeriesCell* __restrict__ cells) {
+  const int64_t i = (int64_t)BID * BLK + threadIdx.x;
+  if (i >= n_slots) return;
+  const uint32_t k = ckey[i];
+  if (k == SERIES_NO_CELL) return;
+  // a tile's slot 1 never continues its slot 0; slot 0 continues the last run of the tile before it
+  if (!(i & 1) && i > 0 && (ckey[i - 1] == SERIES_NO_CELL ? ckey[i - 2] : ckey[i - 1]) == k) return;
+  SwSeriesCell c = carry[i];
+  for (int64_t j = i + 1; j < n_slots; ++j) {
+    const uint32_t kj = ckey[j];
+    if (kj == SERIES_NO_CELL) continue;
+    if (kj != k) break;
+    series_merge(c, carry[j]);
+  }
+  if ((int64_t)k < n_cells) cells[k] = c;
+}
+
 // ============================================================================ reject refs
 // Snapshot of a step's rejected events for the host slow path, taken on the compute stream right
 // after the process phase (the next step overwrites the reject list).  Duplicates are dropped here
@@ -2175,6 +2347,41 @@ int sw_store_filter(const uint8_t* etype, const int32_t* asg, const int64_t* dat
   if (n_rows > 0)
     k_store_filter<<<grid_for(n_rows), BLK, 0, s>>>(etype, asg, date, n_rows, et, bits, n_asg, lo, hi, out_rows, cap,
                                                     n_match);
+  return (int)hipGetLastError();
+}
+
+// Bucketed series, first half: per-wave match counts into sums [q->grid * 4], totals into counters
+// (u32[2]: matches, NaN rows).  The host reads the totals back to size the pair buffers.
+int sw_store_series_count(const SwSeriesQuery* q, uint32_t* sums, uint32_t* counters, hipStream_t s) {
+  if (q->n_names < 1 || q->n_names > SW_SERIES_MAX_NAMES || q->bucket_ms < 1 || q->n_buckets < 1 ||
+      q->n_names * q->n_buckets > SW_SERIES_MAX_CELLS || q->grid < 1 || q->rounds < 1 ||
+      q->grid * WAVES * q->rounds * 64 < q->n_rows)
+    return (int)hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(uint32_t), s);
+  if (e != hipSuccess) return (int)e;
+  k_series_count<<<(unsigned)q->grid, BLK, 0, s>>>(*q, sums, counters);
+  return (int)hipGetLastError();
+}
+
+// Second half: n_match = counters[0] as read back (> 0).  keys / rows: [2][cap] sort buffers, cap >=
+// n_match; rstate: sw_radix_tmp_words(cap) words; carry / ckey: two slots per 256-pair tile; cells:
+// [n_names * n_buckets], zeroed here.
+int sw_store_series(const SwSeriesQuery* q, const uint32_t* sums, const uint32_t* counters, int64_t n_match,
+                    uint32_t* keys, uint32_t* rows, int64_t cap, uint32_t* rstate, SwSeriesCell* carry, uint32_t* ckey,
+                    SwSeriesCell* cells, hipStream_t s) {
+  const int64_t n_cells = q->n_names * q->n_buckets;
+  if (n_match < 1 || n_match > cap || n_cells < 1 || n_cells > SW_SERIES_MAX_CELLS) return (int)hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(cells, 0, (size_t)n_cells * sizeof(SwSeriesCell), s);
+  if (e != hipSuccess) return (int)e;
+  k_series_emit<<<(unsigned)q->grid, BLK, 0, s>>>(*q, sums, keys, rows, cap);
+  int bits = 0;
+  while (((int64_t)1 << bits) < n_cells) ++bits;
+  const int buf = sw_radix_sort_u32(keys, rows, counters, cap, bits, rstate, nullptr, s);
+  if (buf < 0) return -buf;
+  const int64_t tiles = (n_match + BLK - 1) / BLK;
+  k_series_reduce<<<(unsigned)tiles, BLK, 0, s>>>(*q, keys + buf * cap, rows + buf * cap, counters, n_cells, cells, carry,
+                                                  ckey);
+  k_series_carry<<<(unsigned)((2 * tiles + BLK - 1) / BLK), BLK, 0, s>>>(carry, ckey, 2 * tiles, n_cells, cells);
   return (int)hipGetLastError();
 }
 

@@ -274,6 +274,40 @@ static_assert(sizeof(SwStepSnapshot) == 128, "SwStepSnapshot is 32 u32 words");
 static_assert(offsetof(SwStepSnapshot, block_bytes) == 64 && offsetof(SwStepSnapshot, n_carry) == 88 &&
               offsetof(SwStepSnapshot, rej_refs) == 96, "SwStepSnapshot layout");
 
+// One (measurement name, time bucket) cell of a bucketed series over the event ring (sw_store_series;
+// SERIES_CELL in sitewhere_amd/models/columnar.py mirrors it).  first / last: the cell's row with the
+// smallest / largest (date, event id).  The device writes store sequences into the two ids; the engine
+// turns them into event ids.  An empty cell is all zero bytes.
+typedef struct SwSeriesCell {
+  int64_t count;
+  double sum, min, max, first, last;
+  int64_t first_date, last_date, first_id, last_id;
+} SwSeriesCell;
+static_assert(sizeof(SwSeriesCell) == 80, "SwSeriesCell is ten 8-byte words");
+
+#define SW_SERIES_MAX_NAMES 64
+#define SW_SERIES_MAX_CELLS 65536
+
+// A bucketed-series query (sw_store_series_count / sw_store_series): every field 8 bytes, so the host
+// builds it as an int64 array (SERIES_QUERY in sitewhere_amd/models/columnar.py names the words).
+typedef struct SwSeriesQuery {
+  const uint8_t* etype;        // ring columns
+  const int32_t* asg;
+  const int64_t* date;
+  const uint64_t* name;
+  const double* v0;
+  int64_t n_rows;              // ring rows in use
+  int64_t seq0;                // store sequence of ring row `head` (0 until the ring wraps)
+  int64_t head;                // oldest ring row (0 until the ring wraps)
+  const uint32_t* bits;        // assignment bitmap
+  int64_t n_asg;               // its bits
+  const uint64_t* names;       // [n_names] measurement-name hashes
+  int64_t n_names;
+  int64_t start, end, bucket_ms, n_buckets;
+  int64_t rounds;              // 64-row rounds per wave of the two filter passes
+  int64_t grid;                // their workgroups: the ring is cut into grid * 4 wave chunks
+} SwSeriesQuery;
+
 #define SW_N_STATS 24
 
 enum {

@@ -304,6 +304,11 @@ class SiteWhereClient:
         return self.get(f"/assignments/{assignment_token}/alerts", **crit)
 
     def measurement_series(self, assignment_token: str, **crit):
+        """Measurements grouped by name (``measurementIds``: comma-separated names; ``startDate`` /
+        ``endDate``).  With ``bucketMs`` (then both dates are required) each name's entries are its
+        non-empty time buckets -- ``bucketStart``, ``count``, ``min``, ``max``, ``mean``, ``first``,
+        ``last``, ``firstDate``, ``lastDate`` -- instead of its raw events; at most 65536 names x
+        buckets per request."""
         return self.get(f"/assignments/{assignment_token}/measurements/series", **crit)
 
     def invoke_command(self, assignment_token: str, command_token: str, parameters: dict | None = None):

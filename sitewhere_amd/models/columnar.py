@@ -126,6 +126,19 @@ STEP_SNAPSHOT = np.dtype([
 ])
 assert STEP_SNAPSHOT.itemsize == 128
 
+# One (measurement name, time bucket) cell of a bucketed series (SwSeriesCell in swengine.h); an empty
+# cell is all zero bytes.  first / last: the row with the smallest / largest (date, event id).
+SERIES_CELL = np.dtype([
+    ("count", "<i8"), ("sum", "<f8"), ("min", "<f8"), ("max", "<f8"), ("first", "<f8"), ("last", "<f8"),
+    ("first_date", "<i8"), ("last_date", "<i8"), ("first_id", "<i8"), ("last_id", "<i8"),
+])
+assert SERIES_CELL.itemsize == 80
+SERIES_MAX_NAMES = 64          # SW_SERIES_MAX_NAMES
+SERIES_MAX_CELLS = 65536       # SW_SERIES_MAX_CELLS
+# The int64 words of a series query (SwSeriesQuery in swengine.h), in order.
+SERIES_QUERY = ("etype", "asg", "date", "name", "v0", "n_rows", "seq0", "head", "bits", "n_asg", "names", "n_names",
+                "start", "end", "bucket_ms", "n_buckets", "rounds", "grid")
+
 # Durable-block encoder state (u64 words): the result words follow the max_pages look-back words
 # (SEG_ST_* in swseg.h) -- block bytes (~0 on error), errors, store sequence of the first row.
 SEG_ST_BYTES, SEG_ST_ERRORS, SEG_ST_FIRST = 1, 2, 3

@@ -671,6 +671,24 @@ class CpuInboundEngine(EngineBase):
         cols = {k: v[page] for k, v in s.items()}
         return len(rows), cols, seq[order[lo:hi]] * self.world + self.rank
 
+    def aggregate_store(self, asg_idx, name_hashes, start, end, bucket_ms):
+        """The oracle of the MI355X series kernels: a numpy filter, then ``series.bucket_series``."""
+        from .series import bucket_series, check_series_args
+        names, n_buckets = check_series_args(name_hashes, start, end, bucket_ms)
+        n = min(self.cursor, self.cfg.store_cap)
+        s = self.store
+        d = s["date"][:n]
+        m = (s["etype"][:n] == EV_MEASUREMENT) & np.isin(s["asg"][:n], np.asarray(list(asg_idx), np.int32))
+        m &= (d >= start) & (d <= end) & np.isin(s["name"][:n], np.asarray(names, np.uint64))
+        rows = np.nonzero(m)[0]
+        pos = {h: i for i, h in enumerate(names)}
+        idx = np.fromiter((pos[int(h)] for h in s["name"][rows]), np.int64, len(rows))
+        eids = self._row_seq(rows.astype(np.int64), self.cursor) * self.world + self.rank
+        cells, n_nan = bucket_series(idx, d[rows], eids, s["v0"][rows], int(start), int(bucket_ms), len(names), n_buckets)
+        wrapped = self.cursor > self.cfg.store_cap
+        hot = int(s["recv"][self.cursor % self.cfg.store_cap]) if wrapped else None
+        return cells, {"rows": len(rows) - n_nan, "nan": n_nan, "hot_since": hot}
+
     def intern_table(self) -> dict:
         """name hash -> dense name id (same form as the GPU and native engines)."""
         return dict(self.intern)

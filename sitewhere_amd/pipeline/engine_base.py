@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .._native import native
-from ..models.columnar import OUT_REC, STAT_NAMES, REG_SLOT
+from ..models.columnar import EV_ALERT, OUT_REC, STAT_NAMES, REG_SLOT
 from .config import EngineConfig
 from .fleet import hash64
 
@@ -138,6 +138,7 @@ class EngineBase:
         self.names: dict[int, str] = {}
         self.presence_hash = hash64(self.PRESENCE)
         self.names[self.presence_hash] = self.PRESENCE
+        self.alert_names: set[int] = set()       # hashes learnt as alert types (the rest name measurements)
         # zones
         self.zones: list[Zone] = []
         self.tests: list[ZoneTest] = []
@@ -311,6 +312,8 @@ class EngineBase:
                 s = bytes(raw[int(r["off"]):int(r["off"]) + int(r["len"])]).decode("utf-8", "replace")
                 self.names[h] = s
                 new[h] = s
+                if int(r["etype"]) == EV_ALERT:
+                    self.alert_names.add(h)
         return new
 
     def name_of(self, h: int) -> str | None:
@@ -425,6 +428,19 @@ class EngineBase:
         """Events of one type for a set of assignment indices in a date range, newest first (ties:
         latest event id first), straight from this shard's event ring -- the hot half of
         ``DeviceEventManagement.list*ForIndex``.  Returns (total, page columns dict, page event ids)."""
+        raise NotImplementedError
+
+    def aggregate_store(self, asg_idx, name_hashes, start: int, end: int, bucket_ms: int):
+        """Measurement series in time buckets from this shard's event ring: measurement rows of the
+        assignments ``asg_idx`` whose name is one of ``name_hashes`` (``hash64`` of the name, at most 64,
+        no duplicates) and whose date lies in [start, end] land in cell (position of the name,
+        (date - start) // bucket_ms).  Returns (cells, info): ``cells`` is a ``SERIES_CELL`` array of
+        shape (names, (end - start) // bucket_ms + 1), at most 65536 cells, an empty cell all zero,
+        ids being event ids as in :meth:`query_store`; ``info`` has ``rows`` (rows reduced), ``nan``
+        (rows skipped because their value is NaN) and ``hot_since`` (received date of the oldest row
+        once the ring has wrapped -- rows received before it are gone -- else None).  ``ValueError`` on
+        arguments outside those limits.  An addition over the reference, whose series endpoint only
+        regroups raw events."""
         raise NotImplementedError
 
     @staticmethod

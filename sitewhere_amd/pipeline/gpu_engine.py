@@ -1281,15 +1281,20 @@ class GpuInboundEngine(EngineBase):
         with self._lock:
             return self._query_store(event_type, asg_idx, start, end, page_number, page_size)
 
-    def _query_store(self, event_type, asg_idx, start, end, page_number, page_size):
-        cur = self.cursor
-        n = min(cur, self.cfg.store_cap)
+    def _asg_bitmap(self, asg_idx):
+        """An assignment set as a bitmap over ``max_assignments`` in HBM (the hot-store kernels' set test)."""
         nbits = self.cfg.max_assignments
         words = np.zeros((nbits + 31) // 32, np.uint32)
         a = np.asarray(list(asg_idx), np.int64)
         a = a[(a >= 0) & (a < nbits)]
         np.bitwise_or.at(words, a >> 5, (np.uint32(1) << (a & 31).astype(np.uint32)))
-        bits = torch.from_numpy(words.view(np.int32)).to(self.device)
+        return torch.from_numpy(words.view(np.int32)).to(self.device)
+
+    def _query_store(self, event_type, asg_idx, start, end, page_number, page_size):
+        cur = self.cursor
+        n = min(cur, self.cfg.store_cap)
+        nbits = self.cfg.max_assignments
+        bits = self._asg_bitmap(asg_idx)
         if getattr(self, "_q_rows", None) is None or self._q_rows.numel() < max(n, 1):
             self._q_rows = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
             self._q_n = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -1313,6 +1318,72 @@ class GpuInboundEngine(EngineBase):
         for k in ("name", "alt", "aux"):
             cols[k] = cols[k].view(np.uint64)
         return total, cols, seq[sel].cpu().numpy() * self.world + self.rank
+
+    def aggregate_store(self, asg_idx, name_hashes, start, end, bucket_ms):
+        """Bucketed series on the MI355X (``sw_store_series``, csrc/hip/swgpu.hip): two filter passes
+        over the HBM ring compact (cell, row) pairs in ring order, a stable radix sort groups them by
+        cell and a tiled reduction folds each cell in that fixed order -- no floating-point atomics, so
+        an unchanged ring gives the same bytes every time.  Only the cells cross PCIe.  Runs on the
+        caller's current stream in buffers of its own, outside the captured step graph; holds the
+        engine lock like :meth:`query_store`."""
+        from .series import check_series_args
+        names, n_buckets = check_series_args(name_hashes, start, end, bucket_ms)
+        with self._lock:
+            return self._aggregate_store(asg_idx, names, int(start), int(end), int(bucket_ms), n_buckets)
+
+    def _series_buf(self, key: str, n: int, dtype=torch.int32):
+        bufs = self.__dict__.setdefault("_s_bufs", {})
+        b = bufs.get(key)
+        if b is None or b.numel() < n:
+            b = bufs[key] = torch.empty(n, dtype=dtype, device=self.device)
+        return b
+
+    def _aggregate_store(self, asg_idx, names, start, end, bucket_ms, n_buckets):
+        from ..models.columnar import SERIES_CELL, SERIES_QUERY
+        cur = self.cursor
+        ring = self.cfg.store_cap
+        n = min(cur, ring)
+        n_cells = len(names) * n_buckets
+        info = {"rows": 0, "nan": 0, "hot_since": None}
+        if n == 0:
+            return np.zeros((len(names), n_buckets), SERIES_CELL), info
+        st = self.store
+        head = cur % ring if cur > ring else 0
+        if cur > ring:
+            info["hot_since"] = int(st["recv"][head].item())
+        nbits = self.cfg.max_assignments
+        bits = self._asg_bitmap(asg_idx)
+        nm = torch.from_numpy(np.asarray(names, np.uint64).view(np.int64)).to(self.device)
+        # each wave of the two filter passes owns `rounds` runs of 64 ring rows, in at most 2048 workgroups
+        rounds = max(1, -(-n // (256 * 2048)))
+        grid = -(-n // (256 * rounds))
+        sums, counters = self._series_buf("sums", 4 * grid), self._series_buf("counters", 2)
+        q = dict(etype=_ptr(st["etype"]), asg=_ptr(st["asg"]), date=_ptr(st["date"]), name=_ptr(st["name"]),
+                 v0=_ptr(st["v0"]), n_rows=n, seq0=cur - n, head=head, bits=_ptr(bits), n_asg=nbits, names=_ptr(nm),
+                 n_names=len(names), start=start, end=end, bucket_ms=bucket_ms, n_buckets=n_buckets, rounds=rounds,
+                 grid=grid)
+        q = np.array([q[k] for k in SERIES_QUERY], np.int64)
+        stream = self._stream()
+        _chk(self.lib.sw_store_series_count(q.ctypes.data, _ptr(sums), _ptr(counters), stream), "sw_store_series_count")
+        n_match, n_nan = (int(x) for x in counters.cpu().numpy().view(np.uint32))
+        info["rows"], info["nan"] = n_match, n_nan
+        if n_match == 0:
+            return np.zeros((len(names), n_buckets), SERIES_CELL), info
+        # the sort sizes its grid by the capacity: keep it near the match count, not the ring size
+        cap = -(-n_match // 4096) * 4096
+        tiles = -(-n_match // 256)
+        keys, rows = self._series_buf("keys", 2 * cap), self._series_buf("rows", 2 * cap)
+        rstate = self._series_buf("rstate", int(self.lib.sw_radix_tmp_words(cap)))
+        carry = self._series_buf("carry", 2 * tiles * 10, torch.int64)
+        ckey = self._series_buf("ckey", 2 * tiles)
+        dcells = self._series_buf("cells", n_cells * 10, torch.int64)
+        _chk(self.lib.sw_store_series(q.ctypes.data, _ptr(sums), _ptr(counters), n_match, _ptr(keys), _ptr(rows), cap,
+                                      _ptr(rstate), _ptr(carry), _ptr(ckey), _ptr(dcells), stream), "sw_store_series")
+        cells = dcells[:n_cells * 10].cpu().numpy().view(SERIES_CELL).reshape(len(names), n_buckets)
+        full = cells["count"] > 0
+        for f in ("first_id", "last_id"):            # the device wrote store sequences
+            cells[f][full] = cells[f][full] * self.world + self.rank
+        return cells, info
 
     def store_rows(self):
         cur = self.cursor

@@ -1339,6 +1339,45 @@ class GpuInboundApi:
             out.append(ev)
         return {"numResults": int(total), "results": out}
 
+    def measurement_series_hot(self, index: str, entity_ids: list, measurement_ids: list | None, start_date: int,
+                               end_date: int, bucket_ms: int) -> dict:
+        """Measurement series in time buckets from the engine's event ring
+        (``EngineBase.aggregate_store``: on the MI355X the scan and the reduction run in HBM and only
+        the cells cross PCIe).  ``measurement_ids`` None: every name the engine knows that is neither an
+        alert type nor a rule's type.  One engine call per 64 names.  Returns ``{"hotSince", "rows",
+        "series"}``: ``series`` holds, per name that has rows (sorted by name), its non-empty buckets
+        in ascending order; ``hotSince`` is the received date of the oldest ring row once the ring has
+        wrapped (rows received earlier are gone: the caller decides whether the ring covers its range),
+        else None."""
+        from ..models.columnar import SERIES_MAX_NAMES
+        from ..pipeline.fleet import hash64
+        from ..pipeline.series import series_buckets, series_entries
+        e = self._e
+        eng = e.engine
+        pos = self._INDEX[index]
+        want = set(entity_ids)
+        with e._lock:
+            asg = [ai for ai, a in e._asg_entities.items()
+                   if (a.id, a.device_id, a.customer_id, a.area_id, a.asset_id)[pos] in want]
+        if measurement_ids is None:
+            skip = set(eng.alert_names) | {hash64(t.alert_type) for t in eng.rule_tests} | {eng.presence_hash}
+            names = sorted(n for h, n in list(eng.names.items()) if h not in skip)
+        else:
+            names = sorted(set(measurement_ids))
+        out = {"hotSince": None, "rows": 0, "series": []}
+        if not names:
+            series_buckets(1, start_date, end_date, bucket_ms)        # the range checks still apply
+        for k in range(0, len(names), SERIES_MAX_NAMES):
+            chunk = names[k:k + SERIES_MAX_NAMES]
+            cells, info = eng.aggregate_store(asg, [hash64(n) for n in chunk], start_date, end_date, bucket_ms)
+            out["hotSince"] = info["hot_since"]
+            out["rows"] += info["rows"]
+            for n, row in zip(chunk, cells):
+                entries = series_entries(row, start_date, bucket_ms)
+                if entries:
+                    out["series"].append({"measurementId": n, "entries": entries})
+        return out
+
     def process_payloads(self, payloads: list) -> dict:
         """Synchronous injection (tests / REST): one engine step over the given wire payloads."""
         raw, offs = pack_messages([bytes(p) for p in payloads])

@@ -310,6 +310,11 @@ class InboundProcessingApi:
                 "unregisteredEvents": e.unregistered.count, "deviceCacheHits": e.devices.hits,
                 "deviceCacheMisses": e.devices.misses}
 
+    def measurement_series_hot(self, index, entity_ids, measurement_ids, start_date, end_date, bucket_ms):
+        """Bucketed series from a hot store (``GpuInboundApi.measurement_series_hot``): the per-event
+        engine keeps none, so None -- the caller buckets event management's list instead."""
+        return None
+
 
 class InboundProcessingMicroservice(MultitenantMicroservice):
     identifier = "inbound-processing"

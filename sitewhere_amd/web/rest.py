@@ -93,6 +93,32 @@ def date_paging(page: int = 1, pageSize: int = 100, startDate: str | None = None
     return {"pageNumber": page, "pageSize": pageSize, "startDate": _date(startDate), "endDate": _date(endDate)}
 
 
+def bucketed_series(c, assignment_id: str, start, end, measurement_ids: str | None, bucket_ms: int) -> list:
+    """``measurements/series?bucketMs=``: one entry per non-empty time bucket instead of one per event
+    (an addition over the reference).  Served from the inbound engine's event ring when the tenant has
+    one and the ring covers the range -- it has not wrapped, or ``startDate >= hotSince`` (an evicted
+    row was received before ``hotSince``, and an event is not dated after it was received; events dated
+    in the future break that rule and can be missed) -- else from event management's list, bucketed
+    on the host by the same function (``pipeline/series.py``).  The same shape on both routes."""
+    from ..pipeline.series import host_series, series_buckets
+    if start is None or end is None:
+        raise SiteWhereSystemException(ErrorCode.IncompleteData, detail="bucketMs requires startDate and endDate")
+    want = sorted(set(measurement_ids.split(","))) if measurement_ids else None
+    try:
+        n_buckets = series_buckets(1, start, end, bucket_ms)
+        if want is not None and len(want) * n_buckets > 65536:
+            raise ValueError(f"{len(want)} names x {n_buckets} buckets exceed 65536 cells")
+        hot = c.svc("InboundProcessing").measurement_series_hot("Assignment", [assignment_id], want, start, end,
+                                                                 bucket_ms)
+    except ValueError as e:
+        raise SiteWhereSystemException(ErrorCode.IncompleteData, detail=str(e)) from None
+    if hot is not None and (hot["hotSince"] is None or start >= hot["hotSince"]):
+        return hot["series"]
+    ms = c.em.list_measurements_for_index("Assignment", [assignment_id],
+                                          {"pageNumber": 1, "pageSize": 0, "startDate": start, "endDate": end}).results
+    return host_series(ms, None if want is None else set(want), start, end, bucket_ms)
+
+
 # ------------------------------------------------------------------------------ request context
 class _Bound:
     """Service proxy that runs every call inside the caller's security context."""
@@ -710,7 +736,9 @@ def assignments_router() -> APIRouter:
 
     @r.get("/{token}/measurements/series")
     def series(token: str, page: int = 1, pageSize: int = 0, startDate: str | None = None, endDate: str | None = None,
-               measurementIds: str | None = None, c: Ctx = TENANT):
+               measurementIds: str | None = None, bucketMs: int | None = None, c: Ctx = TENANT):
+        if bucketMs is not None:
+            return bucketed_series(c, asg(c, token).id, _date(startDate), _date(endDate), measurementIds, bucketMs)
         ms = c.em.list_measurements_for_index("Assignment", [asg(c, token).id],
                                               date_paging(page, pageSize, startDate, endDate)).results
         want = set(measurementIds.split(",")) if measurementIds else None
