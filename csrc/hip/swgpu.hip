@@ -1883,6 +1883,137 @@ __global__ __launch_bounds__(BLK) void k_series_carry(const SwSeriesCell* __rest
   if ((int64_t)k < n_cells) cells[k] = c;
 }
 
+// ============================================================================ hot-store near
+// Locations near a point straight from the ring (sw_store_near; the search SPI's getLocationsNear):
+// location rows of an assignment set in [start, end] whose haversine distance to the centre is at most
+// radius_m.  One pass: the 1-byte type column for every row, assignment and date where the type
+// matches, latitude and longitude for candidates, the fp64 trigonometry only for candidates inside the
+// host's conservative box (pipeline/near.py: near_box).  Matches are compacted as (ring row, distance),
+// wave by wave with a ballot -- unordered; the host orders the match set on the device.  latest: k_near_best<0> and <1> run ahead and leave each assignment's newest valid
+// candidate in best_date / best_seq (integer atomicMax: the same in any order); the filter then keeps a
+// row only if it is that one.  No floating-point atomics.
+enum { NEAR_NO = 0, NEAR_INVALID = 1, NEAR_VALID = 2 };
+
+// The row's class; for a candidate (valid or not) *a, *d, *lat, *lon are its columns.
+__device__ __forceinline__ int near_candidate(const SwNearQuery& q, int64_t r, int32_t* a, int64_t* d, double* lat,
+                                              double* lon) {
+  if (r >= q.n_rows || q.etype[r] != (uint8_t)SW_EV_LOCATION) return NEAR_NO;
+  *a = q.asg[r];
+  if (*a < 0 || *a >= q.n_asg || !((q.bits[*a >> 5] >> (*a & 31)) & 1u)) return NEAR_NO;
+  *d = q.date[r];
+  if (*d < q.start || *d > q.end) return NEAR_NO;
+  *lat = q.v0[r];
+  *lon = q.v1[r];
+  // written so that a NaN fails: not finite, or outside [-90, 90] x [-180, 180]
+  return (fabs(*lat) <= 90.0 && fabs(*lon) <= 180.0) ? NEAR_VALID : NEAR_INVALID;
+}
+
+__device__ __forceinline__ int64_t near_seq(const SwNearQuery& q, int64_t r) {
+  return q.seq0 + (r >= q.head ? r - q.head : r - q.head + q.n_rows);
+}
+
+// core/geo.py haversine_m, operation for operation (no contraction into fma: the numpy oracle has none).
+__device__ __forceinline__ double near_haversine(double p1, double cos_p1, double lon1, double lat2, double lon2) {
+#pragma clang fp contract(off)
+  const double rad = 3.141592653589793 / 180.0;
+  const double p2 = lat2 * rad;
+  const double dp = p2 - p1, dl = (lon2 - lon1) * rad;
+  const double s1 = sin(dp / 2), s2 = sin(dl / 2);
+  const double a = s1 * s1 + cos_p1 * cos(p2) * (s2 * s2);
+  return (2 * 6371000.0) * asin(sqrt(a));
+}
+
+// PASS 0: best_date[a] = newest date among a's valid candidates; PASS 1: best_seq[a] = largest store
+// sequence among those at that date.  The plain read ahead of the atomic saves most atomics on a ring
+// that is roughly chronological; a stale read only costs a redundant one.
+template <int PASS>
+__global__ __launch_bounds__(BLK) void k_near_best(const SwNearQuery q) {
+  const int64_t stride = (int64_t)gridDim.x * BLK;
+  for (int64_t r = (int64_t)BID * BLK + threadIdx.x; r < q.n_rows; r += stride) {
+    int32_t a;
+    int64_t d;
+    double lat, lon;
+    if (near_candidate(q, r, &a, &d, &lat, &lon) != NEAR_VALID) continue;   // a is inside [0, n_asg) here
+    if (PASS == 0) {
+      if (q.best_date[a] < d) atomicMax((long long*)&q.best_date[a], (long long)d);
+    } else if (q.best_date[a] == d) {
+      const int64_t s = near_seq(q, r);
+      if (q.best_seq[a] < s) atomicMax((long long*)&q.best_seq[a], (long long)s);
+    }
+  }
+}
+
+// counters: [0] matches (past cap too), [1] candidates, [2] invalid candidates.  A workgroup takes
+// chunks of NEAR_CHUNK rows; each wave places its matches in the workgroup's LDS stage (ballot + one LDS
+// integer atomic per wave that has any), then the workgroup reserves its output range with one global
+// atomic and copies the stage out.  One global atomic per wave, as k_store_filter has, was measured at
+// 24 ms over a 2^27-row ring when most waves have a match (2.1M atomics on one address).
+#define NEAR_U 4
+#define NEAR_CHUNK (BLK * NEAR_U)
+__global__ __launch_bounds__(BLK) void k_near_filter(const SwNearQuery q, uint32_t* __restrict__ out_rows,
+                                                     double* __restrict__ out_dist, int64_t cap,
+                                                     uint32_t* __restrict__ counters) {
+  __shared__ uint32_t s_rows[NEAR_CHUNK];
+  __shared__ double s_dist[NEAR_CHUNK];
+  __shared__ uint32_t s_n, s_cnt, s_base;
+  // every thread runs the same number of rounds (the ballots need whole waves, the barriers the workgroup)
+  const int64_t n_chunks = (q.n_rows + NEAR_CHUNK - 1) / NEAR_CHUNK;
+  const int64_t iters = (n_chunks + gridDim.x - 1) / gridDim.x;
+  const double p1 = q.lat * (3.141592653589793 / 180.0), cos_p1 = cos(p1);
+  const bool wraps = q.lon_lo > q.lon_hi;
+  uint32_t n_cand = 0, n_bad = 0;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t row0 = ((int64_t)BID + it * gridDim.x) * NEAR_CHUNK;       // past the ring: no row passes
+    for (int u = 0; u < NEAR_U; ++u) {
+      const int64_t r = row0 + u * BLK + threadIdx.x;
+      int32_t a = 0;
+      int64_t d = 0;
+      double lat = 0.0, lon = 0.0, dist = 0.0;
+      const int cls = near_candidate(q, r, &a, &d, &lat, &lon);
+      bool hit = false;
+      if (cls == NEAR_VALID && (!q.latest || (q.best_date[a] == d && q.best_seq[a] == near_seq(q, r))) &&
+          lat >= q.lat_lo && lat <= q.lat_hi &&
+          (wraps ? (lon >= q.lon_lo || lon <= q.lon_hi) : (lon >= q.lon_lo && lon <= q.lon_hi))) {
+        dist = near_haversine(p1, cos_p1, q.lon, lat, lon);
+        hit = dist <= q.radius_m;
+      }
+      n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
+      n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
+      const ull mask = __ballot(hit);
+      if (!mask) continue;
+      uint32_t base = 0;
+      if (lane_id() == 0) base = atomicAdd(&s_n, (uint32_t)__popcll(mask));
+      base = __shfl(base, 0, 64);
+      if (hit) {
+        const uint32_t pos = base + (uint32_t)__popcll(mask & lanemask_lt());
+        if (pos < NEAR_CHUNK) { s_rows[pos] = (uint32_t)r; s_dist[pos] = dist; }
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                   // publish the round's count, reserve its range
+      const uint32_t m = s_n < NEAR_CHUNK ? s_n : NEAR_CHUNK; // at most one match per row of the chunk
+      s_cnt = m;
+      s_n = 0;
+      if (m) s_base = atomicAdd(&counters[0], m);
+    }
+    __syncthreads();                                          // s_cnt stays as it is until the next round's publish
+    const uint32_t n = s_cnt;
+    if (n == 0) continue;                                     // the whole workgroup
+    const int64_t base = s_base;
+    for (uint32_t i = threadIdx.x; i < n; i += BLK) {
+      const int64_t pos = base + i;
+      if (pos < cap) { out_rows[pos] = s_rows[i]; out_dist[pos] = s_dist[i]; }
+    }
+    __syncthreads();                                          // the stage is free for the next round
+  }
+  if (lane_id() == 0) {
+    if (n_cand) atomicAdd(&counters[1], n_cand);
+    if (n_bad) atomicAdd(&counters[2], n_bad);
+  }
+}
+
 // ============================================================================ reject refs
 // Snapshot of a step's rejected events for the host slow path, taken on the compute stream right
 // after the process phase (the next step overwrites the reject list).  Duplicates are dropped here
@@ -2385,6 +2516,27 @@ int sw_store_series(const SwSeriesQuery* q, const uint32_t* sums, const uint32_t
   return (int)hipGetLastError();
 }
 
+// Locations near a point: matches of *q as (ring row, distance) into out_rows / out_dist [cap], unordered;
+// counters (u32[3], zeroed here): matches (the total even past cap), candidates, invalid candidates.
+// q->latest: best_date / best_seq [n_asg] hold INT64_MIN on entry.  The query is refused, before any
+// launch, unless the centre, the radius and the box are finite and in range.
+int sw_store_near(const SwNearQuery* q, uint32_t* out_rows, double* out_dist, int64_t cap, uint32_t* counters,
+                  hipStream_t s) {
+  const bool centre = fabs(q->lat) <= 90.0 && fabs(q->lon) <= 180.0 && q->radius_m >= 0.0 && q->radius_m <= 1.0e7;
+  const bool box = q->lat_lo <= q->lat_hi && fabs(q->lon_lo) <= 180.0 && fabs(q->lon_hi) <= 180.0;
+  if (!centre || !box || q->start > q->end || q->n_rows < 1 || q->n_rows > ((int64_t)1 << 32) || q->n_asg < 1 ||
+      cap < 1 || q->head < 0 || q->head >= q->n_rows || (q->latest && (!q->best_date || !q->best_seq)))
+    return (int)hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(counters, 0, 3 * sizeof(uint32_t), s);
+  if (e != hipSuccess) return (int)e;
+  if (q->latest) {
+    k_near_best<0><<<grid_for(q->n_rows), BLK, 0, s>>>(*q);
+    k_near_best<1><<<grid_for(q->n_rows), BLK, 0, s>>>(*q);
+  }
+  k_near_filter<<<grid_for((q->n_rows + NEAR_U - 1) / NEAR_U), BLK, 0, s>>>(*q, out_rows, out_dist, cap, counters);
+  return (int)hipGetLastError();
+}
+
 int sw_state_lookup(const SwMsSlot* ms, int64_t mask, int32_t asg, int32_t n_ids, SwMsSlot* out, uint32_t* n_out,
                     hipStream_t s) {
   hipError_t e = hipMemsetAsync(n_out, 0, sizeof(uint32_t), s);
@@ -2513,6 +2665,7 @@ int sw_abi_sizes(int64_t* out) {
   out[8] = sizeof(SwWireRec);
   out[9] = sizeof(SwStrRef);
   out[10] = sizeof(SwStepSnapshot);
+  out[11] = sizeof(SwNearQuery);
   return 0;
 }
 

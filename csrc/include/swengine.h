@@ -308,6 +308,30 @@ typedef struct SwSeriesQuery {
   int64_t grid;                // their workgroups: the ring is cut into grid * 4 wave chunks
 } SwSeriesQuery;
 
+// A locations-near query (sw_store_near_best / sw_store_near): every field 8 bytes, so the host builds
+// it as an int64 array, the doubles by their bits (NEAR_QUERY in sitewhere_amd/models/columnar.py names
+// the words).  The box is the host's conservative cover of the cap (pipeline/near.py: near_box), in
+// degrees; lon_lo > lon_hi: the longitude interval wraps across +-180.
+typedef struct SwNearQuery {
+  const uint8_t* etype;        // ring columns
+  const int32_t* asg;
+  const int64_t* date;
+  const double* v0;            // latitude
+  const double* v1;            // longitude
+  int64_t n_rows;              // ring rows in use
+  int64_t seq0;                // store sequence of ring row `head` (0 until the ring wraps)
+  int64_t head;                // oldest ring row (0 until the ring wraps)
+  const uint32_t* bits;        // assignment bitmap
+  int64_t n_asg;               // its bits, and the entries of the two tables below
+  int64_t start, end;
+  double lat, lon, radius_m;   // centre (degrees) and radius
+  double lat_lo, lat_hi, lon_lo, lon_hi;
+  int64_t latest;              // 1: keep a row only if it is its assignment's newest valid candidate
+  int64_t* best_date;          // [n_asg] latest only: date of that row, then its store sequence
+  int64_t* best_seq;
+} SwNearQuery;
+static_assert(sizeof(SwNearQuery) == 176, "SwNearQuery is 22 8-byte words");
+
 #define SW_N_STATS 24
 
 enum {

@@ -340,3 +340,10 @@ class SiteWhereClient:
 
     def search_device_states(self, criteria: dict | None = None):
         return self.post("/devicestates/search", criteria or {})
+
+    def locations_near(self, latitude: float, longitude: float, distance: float, provider_id: str = "events", **crit):
+        """Locations within ``distance`` metres of a point (``startDate`` / ``endDate``; ``latest``: only
+        each assignment's newest location in the range is looked at; ``order``: ``date`` or
+        ``distance``; ``page`` / ``pageSize``).  Search results of locations, each with ``distance``."""
+        return self.get(f"/search/{provider_id}/locations/near", latitude=latitude, longitude=longitude,
+                        distance=distance, **crit)

@@ -138,6 +138,11 @@ SERIES_MAX_CELLS = 65536       # SW_SERIES_MAX_CELLS
 # The int64 words of a series query (SwSeriesQuery in swengine.h), in order.
 SERIES_QUERY = ("etype", "asg", "date", "name", "v0", "n_rows", "seq0", "head", "bits", "n_asg", "names", "n_names",
                 "start", "end", "bucket_ms", "n_buckets", "rounds", "grid")
+# The 8-byte words of a locations-near query (SwNearQuery in swengine.h), in order; NEAR_QUERY_F64 are
+# the doubles among them (written by their bits).
+NEAR_QUERY = ("etype", "asg", "date", "v0", "v1", "n_rows", "seq0", "head", "bits", "n_asg", "start", "end",
+              "lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "latest", "best_date", "best_seq")
+NEAR_QUERY_F64 = ("lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi")
 
 # Durable-block encoder state (u64 words): the result words follow the max_pages look-back words
 # (SEG_ST_* in swseg.h) -- block bytes (~0 on error), errors, store sequence of the first row.

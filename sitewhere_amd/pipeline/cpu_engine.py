@@ -689,6 +689,34 @@ class CpuInboundEngine(EngineBase):
         hot = int(s["recv"][self.cursor % self.cfg.store_cap]) if wrapped else None
         return cells, {"rows": len(rows) - n_nan, "nan": n_nan, "hot_since": hot}
 
+    def near_store(self, lat, lon, radius_m, asg_idx=None, start=None, end=None, latest=False, order="date",
+                   page_number=1, page_size=100):
+        """The oracle of the MI355X near kernels: a numpy filter, then ``near.near_select`` over every
+        candidate (no bounding-box prefilter)."""
+        from .near import check_near_args, near_select
+        lat, lon, radius_m = check_near_args(lat, lon, radius_m, start, end, order)
+        n = min(self.cursor, self.cfg.store_cap)
+        s = self.store
+        d = s["date"][:n]
+        m = s["etype"][:n] == EV_LOCATION
+        if asg_idx is not None:
+            m &= np.isin(s["asg"][:n], np.asarray(list(asg_idx), np.int32))
+        if start is not None:
+            m &= d >= start
+        if end is not None:
+            m &= d <= end
+        rows = np.nonzero(m)[0]
+        seq = self._row_seq(rows.astype(np.int64), self.cursor)
+        sel, dist, n_invalid = near_select(s["asg"][rows], d[rows], seq, s["v0"][rows], s["v1"][rows], lat, lon,
+                                           radius_m, bool(latest), order)
+        lo, hi = self._window(page_number, page_size, len(sel))
+        page = rows[sel[lo:hi]]
+        cols = {k: v[page] for k, v in s.items()}
+        wrapped = self.cursor > self.cfg.store_cap
+        hot = int(s["recv"][self.cursor % self.cfg.store_cap]) if wrapped else None
+        info = {"candidates": len(rows), "invalid": n_invalid, "hot_since": hot}
+        return len(sel), cols, seq[sel[lo:hi]] * self.world + self.rank, dist[lo:hi], info
+
     def intern_table(self) -> dict:
         """name hash -> dense name id (same form as the GPU and native engines)."""
         return dict(self.intern)

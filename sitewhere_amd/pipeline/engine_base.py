@@ -443,6 +443,31 @@ class EngineBase:
         regroups raw events."""
         raise NotImplementedError
 
+    def near_store(self, lat: float, lon: float, radius_m: float, asg_idx=None, start: int | None = None,
+                   end: int | None = None, latest: bool = False, order: str = "date", page_number: int = 1,
+                   page_size: int = 100):
+        """Location rows of this shard's event ring near a point (the search SPI's
+        ``getLocationsNear``).  A row is a candidate when it is a location row, its assignment is in
+        ``asg_idx`` (None: every assignment) and its date lies in [start, end] (None: that side open).
+        A candidate whose latitude or longitude is not finite, or lies outside [-90, 90] / [-180, 180],
+        is invalid: never returned, counted.  A valid candidate matches when its haversine distance
+        (``core/geo.haversine_m``: R = 6371000.0, fp64) to (lat, lon) is at most ``radius_m``.
+        ``latest``: of each assignment only the valid candidate with the largest (date, event id) is
+        looked at, so an assignment whose newest position lies outside the radius is absent even if an
+        older one lies inside.  ``order``: "date" is (date desc, event id desc) as :meth:`query_store`
+        orders; "distance" is (distance asc, date desc, event id desc).
+
+        Returns (total, cols, eids, dist_m, info): matches before paging, the page's columns and event
+        ids as :meth:`query_store` returns them, the page's distances (float64 metres) and ``info`` =
+        ``{"candidates", "invalid", "hot_since"}`` (``hot_since`` as in :meth:`aggregate_store`).
+        ``ValueError`` (``pipeline/near.py: check_near_args``) for a centre outside those ranges, a
+        radius that is negative, not finite or above ``NEAR_MAX_RADIUS_M``, ``start > end`` or an
+        unknown order.  The CPU engines are the oracle; an engine whose sin / cos / asin are not
+        numpy's may differ inside ``NEAR_BAND_M`` (1e-6 m): a row whose oracle distance is within the
+        band of ``radius_m`` may fall either way, a returned distance is within the band of the
+        oracle's, and in distance order two rows closer than the band to each other may swap."""
+        raise NotImplementedError
+
     @staticmethod
     def _window(page_number: int, page_size: int, total: int) -> tuple[int, int]:
         if page_size <= 0:

@@ -1331,8 +1331,8 @@ class GpuInboundEngine(EngineBase):
         with self._lock:
             return self._aggregate_store(asg_idx, names, int(start), int(end), int(bucket_ms), n_buckets)
 
-    def _series_buf(self, key: str, n: int, dtype=torch.int32):
-        bufs = self.__dict__.setdefault("_s_bufs", {})
+    def _series_buf(self, key: str, n: int, dtype=torch.int32, pool: str = "_s_bufs"):
+        bufs = self.__dict__.setdefault(pool, {})
         b = bufs.get(key)
         if b is None or b.numel() < n:
             b = bufs[key] = torch.empty(n, dtype=dtype, device=self.device)
@@ -1384,6 +1384,95 @@ class GpuInboundEngine(EngineBase):
         for f in ("first_id", "last_id"):            # the device wrote store sequences
             cells[f][full] = cells[f][full] * self.world + self.rank
         return cells, info
+
+    def near_store(self, lat, lon, radius_m, asg_idx=None, start=None, end=None, latest=False, order="date",
+                   page_number=1, page_size=100):
+        """Locations near a point on the MI355X (``sw_store_near``, csrc/hip/swgpu.hip): one
+        ``k_near_filter`` pass over the HBM ring tests candidates against the host's conservative box
+        (``near.near_box``) and pays for the fp64 haversine only inside it; matches are compacted as
+        (ring row, distance).  ``latest`` runs two ``k_near_best`` passes ahead (integer atomicMax into
+        per-assignment tables).  The match set is ordered on the device and only the page's columns and
+        distances cross PCIe.  No floating-point atomics and a total order, so an unchanged ring gives
+        the same answer every time.  Runs on the caller's current stream in buffers of its own, outside
+        the captured step graph; holds the engine lock like :meth:`query_store`."""
+        from .near import check_near_args
+        lat, lon, radius_m = check_near_args(lat, lon, radius_m, start, end, order)
+        with self._lock:
+            return self._near_store(lat, lon, radius_m, asg_idx, start, end, bool(latest), order, page_number, page_size)
+
+    _near_rows0 = 1 << 20          # first size of near_store's match buffers, in rows (12 B each)
+
+    def _near_store(self, lat, lon, radius_m, asg_idx, start, end, latest, order, page_number, page_size):
+        from ..models.columnar import NEAR_QUERY, NEAR_QUERY_F64
+        from .near import near_box
+        cur = self.cursor
+        ring = self.cfg.store_cap
+        n = min(cur, ring)
+        st = self.store
+        info = {"candidates": 0, "invalid": 0, "hot_since": None}
+        if n == 0:
+            cols = {k: torch.empty(0, dtype=v.dtype).numpy() for k, v in st.items()}       # host tensors: no launch
+            return 0, self._u64_cols(cols), np.zeros(0, np.int64), np.zeros(0, np.float64), info
+        head = cur % ring if cur > ring else 0
+        if cur > ring:
+            info["hot_since"] = int(st["recv"][head].item())
+        nbits = self.cfg.max_assignments
+        if asg_idx is None:
+            bits = torch.full(((nbits + 31) // 32,), -1, dtype=torch.int32, device=self.device)
+        else:
+            bits = self._asg_bitmap(asg_idx)
+        buf = lambda key, m, dtype=torch.int32: self._series_buf(key, m, dtype, pool="_n_bufs")  # noqa: E731
+        i64 = np.iinfo(np.int64)
+        best = None
+        if latest:
+            best = buf("best", 2 * nbits, torch.int64)
+            best[:2 * nbits].fill_(i64.min)
+        lat_lo, lat_hi, lon_lo, lon_hi = near_box(lat, lon, radius_m)
+        vals = dict(etype=_ptr(st["etype"]), asg=_ptr(st["asg"]), date=_ptr(st["date"]), v0=_ptr(st["v0"]),
+                    v1=_ptr(st["v1"]), n_rows=n, seq0=cur - n, head=head, bits=_ptr(bits), n_asg=nbits,
+                    start=i64.min if start is None else int(start), end=i64.max if end is None else int(end),
+                    lat=lat, lon=lon, radius_m=radius_m, lat_lo=lat_lo, lat_hi=lat_hi, lon_lo=lon_lo, lon_hi=lon_hi,
+                    latest=int(latest), best_date=_ptr(best) if latest else 0,
+                    best_seq=_ptr(best) + 8 * nbits if latest else 0)
+        q = np.zeros(len(NEAR_QUERY), np.int64)
+        qf = q.view(np.float64)
+        for i, k in enumerate(NEAR_QUERY):
+            (qf if k in NEAR_QUERY_F64 else q)[i] = vals[k]
+        counters = buf("counters", 3)
+        # the match buffers start at _near_rows0 rows (or what an earlier query grew them to); when that is
+        # short they grow to the match count and the pass is repeated
+        held = self.__dict__.get("_n_bufs", {}).get("rows")
+        cap = min(n, max(self._near_rows0, 0 if held is None else held.numel()))
+        stream = self._stream()
+        while True:
+            rows, dist = buf("rows", cap), buf("dist", cap, torch.float64)
+            _chk(self.lib.sw_store_near(q.ctypes.data, _ptr(rows), _ptr(dist), cap, _ptr(counters), stream),
+                 "sw_store_near")
+            total, info["candidates"], info["invalid"] = (int(x) for x in counters[:3].cpu().numpy().view(np.uint32))
+            if total <= cap:
+                break
+            cap = total
+            if latest:
+                best[:2 * nbits].fill_(i64.min)
+        rows = rows[:total].long() & 0xFFFFFFFF
+        dist = dist[:total]
+        seq = self._row_seq(rows, cur)
+        # stable sorts, least significant key first: event id desc, date desc, then distance asc
+        o = torch.sort(seq, descending=True, stable=True).indices
+        o = o[torch.sort(st["date"][rows[o]], descending=True, stable=True).indices]
+        if order == "distance":
+            o = o[torch.sort(dist[o], stable=True).indices]
+        lo, hi = self._window(page_number, page_size, total)
+        sel = o[lo:hi]
+        page = rows[sel]
+        cols = self._u64_cols({k: v[page].cpu().numpy() for k, v in st.items()})
+        return total, cols, seq[sel].cpu().numpy() * self.world + self.rank, dist[sel].cpu().numpy(), info
+
+    @staticmethod
+    def _u64_cols(cols):
+        for k in ("name", "alt", "aux"):
+            cols[k] = cols[k].view(np.uint64)
+        return cols
 
     def store_rows(self):
         cur = self.cursor

@@ -1313,6 +1313,12 @@ class GpuInboundApi:
                    if (a.id, a.device_id, a.customer_id, a.area_id, a.asset_id)[pos] in want]
         total, cols, eids = e.engine.query_store(self._ETYPE[event_type], asg, start_date, end_date, page_number,
                                                  page_size)
+        return {"numResults": int(total), "results": [ev for ev, _ in self._hot_events(cols, eids)]}
+
+    def _hot_events(self, cols, eids) -> list:
+        """Ring rows (page columns, event ids) as domain events: (event, position in the page) pairs;
+        a row whose assignment the tenant no longer knows is left out."""
+        e = self._e
         out = []
         rules = {t.alert_type: t.alert_message for t in e.engine.rule_tests}
         for i in range(len(eids)):
@@ -1336,8 +1342,35 @@ class GpuInboundApi:
             else:
                 ev = DeviceStateChange(attribute="presence", type="presence", previous_state="PRESENT",
                                        new_state="NOT_PRESENT", **base)
-            out.append(ev)
-        return {"numResults": int(total), "results": out}
+            out.append((ev, i))
+        return out
+
+    def locations_near_hot(self, latitude: float, longitude: float, distance_m: float, start_date: int | None = None,
+                           end_date: int | None = None, index: str | None = None, entity_ids: list | None = None,
+                           latest: bool = False, order: str = "date", page_number: int = 1,
+                           page_size: int = 100) -> dict:
+        """Locations within ``distance_m`` metres of a point from the engine's event ring
+        (``EngineBase.near_store``: on the MI355X the scan and the distances run in HBM and only the
+        page crosses PCIe) -- the search SPI's ``getLocationsNear``.  ``index`` None: tenant-wide, else
+        the locations of ``entity_ids`` under that index as in :meth:`list_hot_events`.  ``latest``: only
+        each assignment's newest location in the range is looked at.  ``order``: "date" (newest first) or
+        "distance" (nearest first).  Returns ``{"hotSince", "numResults", "results", "distances"}``:
+        ``distances`` are metres, parallel to ``results``; ``hotSince`` is the received date of the
+        oldest ring row once the ring has wrapped (the caller decides whether the ring covers its
+        range), else None.  ``ValueError`` for arguments ``near_store`` refuses."""
+        e = self._e
+        asg = None
+        if index is not None:
+            pos = self._INDEX[index]
+            want = set(entity_ids or [])
+            with e._lock:
+                asg = [ai for ai, a in e._asg_entities.items()
+                       if (a.id, a.device_id, a.customer_id, a.area_id, a.asset_id)[pos] in want]
+        total, cols, eids, dist, info = e.engine.near_store(latitude, longitude, distance_m, asg, start_date, end_date,
+                                                            latest, order, page_number, page_size)
+        evs = self._hot_events(cols, eids)
+        return {"hotSince": info["hot_since"], "numResults": int(total), "results": [ev for ev, _ in evs],
+                "distances": [float(dist[i]) for _, i in evs]}
 
     def measurement_series_hot(self, index: str, entity_ids: list, measurement_ids: list | None, start_date: int,
                                end_date: int, bucket_ms: int) -> dict:

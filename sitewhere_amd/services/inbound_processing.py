@@ -315,6 +315,12 @@ class InboundProcessingApi:
         engine keeps none, so None -- the caller buckets event management's list instead."""
         return None
 
+    def locations_near_hot(self, latitude, longitude, distance_m, start_date=None, end_date=None, index=None,
+                           entity_ids=None, latest=False, order="date", page_number=1, page_size=100):
+        """Locations near a point from a hot store (``GpuInboundApi.locations_near_hot``): the per-event
+        engine keeps none, so None -- the caller filters event management's list instead."""
+        return None
+
 
 class InboundProcessingMicroservice(MultitenantMicroservice):
     identifier = "inbound-processing"

@@ -168,6 +168,11 @@ class SolrSearchProvider:
         body = self._get(url) if self._get else urllib.request.urlopen(url, timeout=10).read()
         return json.loads(body).get("response", {}).get("docs", [])
 
+    def get_locations_near(self, latitude: float, longitude: float, distance: float, criteria=None) -> dict:
+        """No geospatial query is sent to Solr: an empty result, as ``SolrSearchProvider.getLocationsNear``
+        of the reference answers."""
+        return {"hotSince": None, "numResults": 0, "results": [], "distances": []}
+
 
 class EventStoreSearchProvider:
     """In-process provider: ``field:value`` terms (AND) over the tenant's event store."""
@@ -195,6 +200,34 @@ class EventStoreSearchProvider:
                 out.append(d)
         return out
 
+    def get_locations_near(self, latitude: float, longitude: float, distance: float, criteria=None) -> dict:
+        """``IDeviceEventSearchProvider.getLocationsNear``: the tenant's locations within ``distance``
+        metres of a point.  ``criteria``: a date-range criteria object or a dict (``startDate``,
+        ``endDate``, ``pageNumber``, ``pageSize``, and the additions ``latest`` and ``order``).  Served
+        from the inbound engine's event ring when the tenant has one and the ring covers the range --
+        it has not wrapped, or ``startDate >= hotSince`` -- else from event management's list of the
+        range's locations, filtered on the host by the same function (``pipeline/near.py``).  Returns
+        ``{"hotSince", "numResults", "results", "distances"}`` on both routes; ``ValueError`` for a
+        point or a distance out of range."""
+        from ..pipeline.near import check_near_args, host_near
+        c = criteria or {}
+        if not isinstance(c, dict):
+            c = {"startDate": c.start_date, "endDate": c.end_date, "pageNumber": c.page_number, "pageSize": c.page_size}
+        start, end = c.get("startDate"), c.get("endDate")
+        latest, order = bool(c.get("latest", False)), c.get("order") or "date"
+        page, size = int(c.get("pageNumber") or 1), int(c.get("pageSize", 100))
+        check_near_args(latitude, longitude, distance, start, end, order)
+        token = self._e.tenant.token
+        hot = self._e.ms.api("InboundProcessing", token).locations_near_hot(
+            latitude, longitude, distance, start, end, None, None, latest, order, page, size)
+        if hot is not None and (hot["hotSince"] is None or (start is not None and start >= hot["hotSince"])):
+            return hot
+        asgs = self._e.ms.api("DeviceManagement", token).list_device_assignments({"pageNumber": 1, "pageSize": 0})
+        locs = self._e.ms.api("DeviceEventManagement", token).list_locations_for_index(
+            "Assignment", [a.id for a in asgs.results],
+            {"pageNumber": 1, "pageSize": 0, "startDate": start, "endDate": end}).results
+        return host_near(locs, latitude, longitude, distance, start, end, latest, order, page, size)
+
 
 class SearchProviderManager:
     def __init__(self, providers: dict):
@@ -208,6 +241,14 @@ class SearchProviderManager:
         if p is None:
             raise NotFoundException(ErrorCode.Error, f"search provider {provider_id}")
         return p.search(query, rows)
+
+    def get_locations_near(self, provider_id: str, latitude: float, longitude: float, distance: float,
+                           criteria=None) -> dict:
+        """The search SPI's ``getLocationsNear`` on one provider (see the providers' methods)."""
+        p = self._p.get(provider_id)
+        if p is None:
+            raise NotFoundException(ErrorCode.Error, f"search provider {provider_id}")
+        return p.get_locations_near(latitude, longitude, distance, criteria)
 
 
 class EventSearchTenantEngine(MicroserviceTenantEngine):

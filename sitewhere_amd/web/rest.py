@@ -892,6 +892,20 @@ def misc_router(web: WebRest) -> APIRouter:
     def search_raw(providerId: str, body: str = Body(...), c: Ctx = TENANT):
         return c.svc("EventSearch").search(providerId, body)
 
+    @r.get("/search/{providerId}/locations/near")
+    def locations_near(providerId: str, latitude: float, longitude: float, distance: float,
+                       startDate: str | None = None, endDate: str | None = None, latest: bool = False,
+                       order: str = "date", page: int = 1, pageSize: int = 100, c: Ctx = TENANT):
+        """The search SPI's ``getLocationsNear`` (the reference has the method but no route): locations
+        within ``distance`` metres of a point, each carrying its ``distance``."""
+        crit = dict(date_paging(page, pageSize, startDate, endDate), latest=latest, order=order)
+        try:
+            res = c.svc("EventSearch").get_locations_near(providerId, latitude, longitude, distance, crit)
+        except ValueError as e:
+            raise SiteWhereSystemException(ErrorCode.IncompleteData, detail=str(e)) from None
+        return {"numResults": res["numResults"],
+                "results": [dict(out(ev), distance=d) for ev, d in zip(res["results"], res["distances"])]}
+
     # system -----------------------------------------------------------------------------
     @r.get("/system/version")
     def version(c: Ctx = GLOBAL):
