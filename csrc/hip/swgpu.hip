@@ -1673,42 +1673,102 @@ __global__ void k_step_end(SwEngineArgs a, const uint32_t* n_rule_alerts) {
   }
 }
 
-// ============================================================================ C ABI
-// ============================================================================ hot-store query
-// Event-management reads over the HBM event ring (DeviceEventManagement.list*ForIndex,
-// EventManagementImpl.java): rows of one event type whose assignment is in a bitmap and whose
-// event date lies in [lo, hi].  One pass over the ring: the 1-byte type column is read for every
-// row, assignment and date only where the type matches.  Matches are compacted per wave (ballot +
-// one atomic per wave that has any) into out_rows -- unordered; the host orders the (usually small)
-// match set by (date desc, event id desc).  *n_match receives the total even past cap.
-__global__ __launch_bounds__(BLK) void k_store_filter(const uint8_t* __restrict__ etype, const int32_t* __restrict__ asg,
-                                                      const int64_t* __restrict__ date, int64_t n_rows, int32_t et,
-                                                      const uint32_t* __restrict__ bits, int64_t n_asg, int64_t lo,
-                                                      int64_t hi, uint32_t* __restrict__ out_rows, int64_t cap,
-                                                      uint32_t* __restrict__ n_match) {
-  const int64_t stride = (int64_t)gridDim.x * BLK;
-  // every lane of a wave iterates the same number of times (ballot needs the whole wave)
-  const int64_t iters = (n_rows + stride - 1) / stride;
-  int64_t r = (int64_t)BID * BLK + threadIdx.x;
-  for (int64_t it = 0; it < iters; ++it, r += stride) {
-    bool hit = false;
-    if (r < n_rows && etype[r] == (uint8_t)et) {
-      const int32_t a = asg[r];
-      if (a >= 0 && a < n_asg && ((bits[a >> 5] >> (a & 31)) & 1u)) {
-        const int64_t d = date[r];
-        hit = d >= lo && d <= hi;
+// ============================================================================ hot-store queries
+// What the three reads over the HBM event ring share, beside their view of it (SwRingView, swengine.h).
+
+// Store sequence of ring row r: the ring's oldest row is `head`.
+__device__ __forceinline__ int64_t ring_seq(const SwRingView& v, int64_t r) {
+  return v.seq0 + (r >= v.head ? r - v.head : r - v.head + v.n_rows);
+}
+
+// Whether ring row r (any r >= 0) has event type et, an assignment inside the bitmap and a date in
+// [start, end]; *a and *d are the row's assignment and date when it passes.  The read order is the
+// cost: the 1-byte type column is the only one read for every row, the assignment only on a type
+// match, the date only on a bitmap hit.
+__device__ __forceinline__ bool ring_row_test(const SwRingView& v, int64_t r, uint8_t et, int32_t* a, int64_t* d) {
+  if (r >= v.n_rows || v.etype[r] != et) return false;
+  *a = v.asg[r];
+  if (*a < 0 || *a >= v.n_asg || !((v.bits[*a >> 5] >> (*a & 31)) & 1u)) return false;
+  *d = v.date[r];
+  return *d >= v.start && *d <= v.end;
+}
+
+// The match compactor: hit(r, &dist) is asked once for every row of the ring (and for rows past it,
+// which it must fail) and the rows it passes land in out_rows [cap], with their dist in out_dist when
+// DIST, in any order; *n_match grows by the matches, past cap too.  A workgroup takes chunks of
+// STAGE_CHUNK rows; each wave places its matches in the workgroup's LDS stage (ballot + one LDS integer
+// atomic per wave that has any), then the workgroup reserves its output range with one global atomic
+// and copies the stage out.  One global atomic per wave instead was measured at 24 ms over a 2^27-row
+// ring when most waves have a match (2.1M atomics on one address; profiles/hot_near/README.md).
+#define STAGE_U 4
+#define STAGE_CHUNK (BLK * STAGE_U)
+template <bool DIST> struct RingStageDist { double dist[STAGE_CHUNK]; };
+template <> struct RingStageDist<false> {};
+template <bool DIST> struct RingStage : RingStageDist<DIST> {
+  uint32_t rows[STAGE_CHUNK];
+  uint32_t n[2], base;          // matches staged in even / odd rounds; the round's place in the output
+};
+
+template <bool DIST, class Hit>
+__device__ __forceinline__ void ring_compact(int64_t n_rows, uint32_t* __restrict__ out_rows,
+                                             double* __restrict__ out_dist, int64_t cap,
+                                             uint32_t* __restrict__ n_match, Hit hit) {
+  __shared__ RingStage<DIST> st;
+  // every thread runs the same number of rounds (the ballots need whole waves, the barriers the workgroup)
+  const int64_t n_chunks = (n_rows + STAGE_CHUNK - 1) / STAGE_CHUNK;
+  const int64_t iters = (n_chunks + gridDim.x - 1) / gridDim.x;
+  if (threadIdx.x == 0) st.n[0] = st.n[1] = 0;
+  __syncthreads();
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t row0 = ((int64_t)BID + it * gridDim.x) * STAGE_CHUNK;     // past the ring: no row passes
+    uint32_t& staged = st.n[it & 1];
+    for (int u = 0; u < STAGE_U; ++u) {
+      const int64_t r = row0 + u * BLK + threadIdx.x;
+      double dist = 0.0;
+      const bool h = hit(r, &dist);
+      const ull mask = __ballot(h);
+      if (!mask) continue;
+      uint32_t base = 0;
+      if (lane_id() == 0) base = atomicAdd(&staged, (uint32_t)__popcll(mask));
+      base = __shfl(base, 0, 64);
+      if (h) {
+        const uint32_t pos = base + (uint32_t)__popcll(mask & lanemask_lt());
+        if (pos < STAGE_CHUNK) {
+          st.rows[pos] = (uint32_t)r;
+          if constexpr (DIST) st.dist[pos] = dist;
+        }
       }
     }
-    const ull mask = __ballot(hit);
-    if (!mask) continue;
-    uint32_t base = 0;
-    if (lane_id() == 0) base = atomicAdd(n_match, (uint32_t)__popcll(mask));
-    base = __shfl(base, 0, 64);
-    if (hit) {
-      const uint64_t pos = (uint64_t)base + (uint64_t)__popcll(mask & lanemask_lt());
-      if ((int64_t)pos < cap) out_rows[pos] = (uint32_t)r;
+    __syncthreads();
+    // the round's count: nobody adds to it again before the round after next, which lies behind the next
+    // round's barrier, so every thread reads the same value; at most one match per row of the chunk
+    const uint32_t n = staged < STAGE_CHUNK ? staged : STAGE_CHUNK;
+    if (n == 0) continue;                                       // the whole workgroup: one barrier per empty chunk
+    if (threadIdx.x == 0) st.base = atomicAdd(n_match, n);      // reserve the round's range
+    __syncthreads();
+    if (threadIdx.x == 0) staged = 0;                           // every thread has read it
+    const int64_t base = st.base;
+    for (uint32_t i = threadIdx.x; i < n; i += BLK) {
+      const int64_t pos = base + i;
+      if (pos < cap) {
+        out_rows[pos] = st.rows[i];
+        if constexpr (DIST) out_dist[pos] = st.dist[i];
+      }
     }
+    __syncthreads();                                            // the stage is free for the next round
   }
+}
+
+// Event-management reads (DeviceEventManagement.list*ForIndex, EventManagementImpl.java): the rows that
+// pass the row test, compacted into out_rows -- unordered; the host orders the (usually small) match
+// set by (date desc, event id desc).  *n_match receives the total even past cap.
+__global__ __launch_bounds__(BLK) void k_store_filter(const SwRingView v, uint8_t et, uint32_t* __restrict__ out_rows,
+                                                      int64_t cap, uint32_t* __restrict__ n_match) {
+  ring_compact<false>(v.n_rows, out_rows, nullptr, cap, n_match, [&](int64_t r, double*) {
+    int32_t a;
+    int64_t d;
+    return ring_row_test(v, r, et, &a, &d);
+  });
 }
 
 // ============================================================================ hot-store series
@@ -1726,24 +1786,21 @@ __global__ __launch_bounds__(BLK) void k_store_filter(const uint8_t* __restrict_
 //                    runs touching the tile's ends go to the tile's two carry slots
 //   k_series_carry   carry slots are in cell order: the first slot of a cell folds the following
 //                    slots of that cell in tile order and writes the cell
-// The 1-byte type column is the only one read for every row; name, value and the bucket division
-// only for rows that pass the type, assignment and date tests.
+// Name, value and the bucket division are read only for rows that pass the row test.
 #define SERIES_NO_CELL 0xFFFFFFFFu
 
 // The row's cell; -1: no match; -2: a match whose value is NaN (counted, in no cell).
 __device__ __forceinline__ int32_t series_cell(const SwSeriesQuery& q, const uint64_t* names, int64_t r) {
-  if (r >= q.n_rows || q.etype[r] != (uint8_t)SW_EV_MEASUREMENT) return -1;
-  const int32_t a = q.asg[r];
-  if (a < 0 || a >= q.n_asg || !((q.bits[a >> 5] >> (a & 31)) & 1u)) return -1;
-  const int64_t d = q.date[r];
-  if (d < q.start || d > q.end) return -1;
+  int32_t a;
+  int64_t d;
+  if (!ring_row_test(q.ring, r, (uint8_t)SW_EV_MEASUREMENT, &a, &d)) return -1;
   const uint64_t h = q.name[r];
   int32_t i = 0;
   while (i < (int32_t)q.n_names && names[i] != h) ++i;
   if (i == (int32_t)q.n_names) return -1;
   const double v = q.v0[r];
   if (v != v) return -2;
-  return i * (int32_t)q.n_buckets + (int32_t)((d - q.start) / q.bucket_ms);
+  return i * (int32_t)q.n_buckets + (int32_t)((d - q.ring.start) / q.bucket_ms);
 }
 
 __device__ __forceinline__ void series_names_to_lds(const SwSeriesQuery& q, uint64_t* names) {
@@ -1829,8 +1886,8 @@ __global__ __launch_bounds__(BLK) void k_series_reduce(const SwSeriesQuery q, co
     const int64_t row = rows[base + t];
     sk[t] = keys[base + t];
     sv[t] = q.v0[row];
-    sd[t] = q.date[row];
-    ss[t] = q.seq0 + (row >= q.head ? row - q.head : row - q.head + q.n_rows);
+    sd[t] = q.ring.date[row];
+    ss[t] = ring_seq(q.ring, row);
   }
   __syncthreads();
   if (t >= m) return;
@@ -1885,31 +1942,22 @@ __global__ __launch_bounds__(BLK) void k_series_carry(const SwSeriesCell* __rest
 
 // ============================================================================ hot-store near
 // Locations near a point straight from the ring (sw_store_near; the search SPI's getLocationsNear):
-// location rows of an assignment set in [start, end] whose haversine distance to the centre is at most
-// radius_m.  One pass: the 1-byte type column for every row, assignment and date where the type
-// matches, latitude and longitude for candidates, the fp64 trigonometry only for candidates inside the
-// host's conservative box (pipeline/near.py: near_box).  Matches are compacted as (ring row, distance),
-// wave by wave with a ballot -- unordered; the host orders the match set on the device.  latest: k_near_best<0> and <1> run ahead and leave each assignment's newest valid
-// candidate in best_date / best_seq (integer atomicMax: the same in any order); the filter then keeps a
-// row only if it is that one.  No floating-point atomics.
+// location rows that pass the row test and whose haversine distance to the centre is at most radius_m.
+// One pass: latitude and longitude for candidates, the fp64 trigonometry only for candidates inside the
+// host's conservative box (pipeline/near.py: near_box); ring_compact collects (ring row, distance).
+// latest: k_near_best<0> and <1> run ahead and leave each assignment's newest valid candidate in
+// best_date / best_seq (integer atomicMax: the same in any order); the filter then keeps a row only
+// if it is that one.  No floating-point atomics.
 enum { NEAR_NO = 0, NEAR_INVALID = 1, NEAR_VALID = 2 };
 
 // The row's class; for a candidate (valid or not) *a, *d, *lat, *lon are its columns.
 __device__ __forceinline__ int near_candidate(const SwNearQuery& q, int64_t r, int32_t* a, int64_t* d, double* lat,
                                               double* lon) {
-  if (r >= q.n_rows || q.etype[r] != (uint8_t)SW_EV_LOCATION) return NEAR_NO;
-  *a = q.asg[r];
-  if (*a < 0 || *a >= q.n_asg || !((q.bits[*a >> 5] >> (*a & 31)) & 1u)) return NEAR_NO;
-  *d = q.date[r];
-  if (*d < q.start || *d > q.end) return NEAR_NO;
+  if (!ring_row_test(q.ring, r, (uint8_t)SW_EV_LOCATION, a, d)) return NEAR_NO;
   *lat = q.v0[r];
   *lon = q.v1[r];
   // written so that a NaN fails: not finite, or outside [-90, 90] x [-180, 180]
   return (fabs(*lat) <= 90.0 && fabs(*lon) <= 180.0) ? NEAR_VALID : NEAR_INVALID;
-}
-
-__device__ __forceinline__ int64_t near_seq(const SwNearQuery& q, int64_t r) {
-  return q.seq0 + (r >= q.head ? r - q.head : r - q.head + q.n_rows);
 }
 
 // core/geo.py haversine_m, operation for operation (no contraction into fma: the numpy oracle has none).
@@ -1929,7 +1977,7 @@ __device__ __forceinline__ double near_haversine(double p1, double cos_p1, doubl
 template <int PASS>
 __global__ __launch_bounds__(BLK) void k_near_best(const SwNearQuery q) {
   const int64_t stride = (int64_t)gridDim.x * BLK;
-  for (int64_t r = (int64_t)BID * BLK + threadIdx.x; r < q.n_rows; r += stride) {
+  for (int64_t r = (int64_t)BID * BLK + threadIdx.x; r < q.ring.n_rows; r += stride) {
     int32_t a;
     int64_t d;
     double lat, lon;
@@ -1937,77 +1985,35 @@ __global__ __launch_bounds__(BLK) void k_near_best(const SwNearQuery q) {
     if (PASS == 0) {
       if (q.best_date[a] < d) atomicMax((long long*)&q.best_date[a], (long long)d);
     } else if (q.best_date[a] == d) {
-      const int64_t s = near_seq(q, r);
+      const int64_t s = ring_seq(q.ring, r);
       if (q.best_seq[a] < s) atomicMax((long long*)&q.best_seq[a], (long long)s);
     }
   }
 }
 
-// counters: [0] matches (past cap too), [1] candidates, [2] invalid candidates.  A workgroup takes
-// chunks of NEAR_CHUNK rows; each wave places its matches in the workgroup's LDS stage (ballot + one LDS
-// integer atomic per wave that has any), then the workgroup reserves its output range with one global
-// atomic and copies the stage out.  One global atomic per wave, as k_store_filter has, was measured at
-// 24 ms over a 2^27-row ring when most waves have a match (2.1M atomics on one address).
-#define NEAR_U 4
-#define NEAR_CHUNK (BLK * NEAR_U)
+// counters: [0] matches (past cap too), [1] candidates, [2] invalid candidates.
 __global__ __launch_bounds__(BLK) void k_near_filter(const SwNearQuery q, uint32_t* __restrict__ out_rows,
                                                      double* __restrict__ out_dist, int64_t cap,
                                                      uint32_t* __restrict__ counters) {
-  __shared__ uint32_t s_rows[NEAR_CHUNK];
-  __shared__ double s_dist[NEAR_CHUNK];
-  __shared__ uint32_t s_n, s_cnt, s_base;
-  // every thread runs the same number of rounds (the ballots need whole waves, the barriers the workgroup)
-  const int64_t n_chunks = (q.n_rows + NEAR_CHUNK - 1) / NEAR_CHUNK;
-  const int64_t iters = (n_chunks + gridDim.x - 1) / gridDim.x;
   const double p1 = q.lat * (3.141592653589793 / 180.0), cos_p1 = cos(p1);
   const bool wraps = q.lon_lo > q.lon_hi;
   uint32_t n_cand = 0, n_bad = 0;
-  if (threadIdx.x == 0) s_n = 0;
-  __syncthreads();
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t row0 = ((int64_t)BID + it * gridDim.x) * NEAR_CHUNK;       // past the ring: no row passes
-    for (int u = 0; u < NEAR_U; ++u) {
-      const int64_t r = row0 + u * BLK + threadIdx.x;
-      int32_t a = 0;
-      int64_t d = 0;
-      double lat = 0.0, lon = 0.0, dist = 0.0;
-      const int cls = near_candidate(q, r, &a, &d, &lat, &lon);
-      bool hit = false;
-      if (cls == NEAR_VALID && (!q.latest || (q.best_date[a] == d && q.best_seq[a] == near_seq(q, r))) &&
-          lat >= q.lat_lo && lat <= q.lat_hi &&
-          (wraps ? (lon >= q.lon_lo || lon <= q.lon_hi) : (lon >= q.lon_lo && lon <= q.lon_hi))) {
-        dist = near_haversine(p1, cos_p1, q.lon, lat, lon);
-        hit = dist <= q.radius_m;
-      }
-      n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
-      n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
-      const ull mask = __ballot(hit);
-      if (!mask) continue;
-      uint32_t base = 0;
-      if (lane_id() == 0) base = atomicAdd(&s_n, (uint32_t)__popcll(mask));
-      base = __shfl(base, 0, 64);
-      if (hit) {
-        const uint32_t pos = base + (uint32_t)__popcll(mask & lanemask_lt());
-        if (pos < NEAR_CHUNK) { s_rows[pos] = (uint32_t)r; s_dist[pos] = dist; }
-      }
+  ring_compact<true>(q.ring.n_rows, out_rows, out_dist, cap, &counters[0], [&](int64_t r, double* dist) {
+    int32_t a = 0;
+    int64_t d = 0;
+    double lat = 0.0, lon = 0.0;
+    const int cls = near_candidate(q, r, &a, &d, &lat, &lon);
+    bool hit = false;
+    if (cls == NEAR_VALID && (!q.latest || (q.best_date[a] == d && q.best_seq[a] == ring_seq(q.ring, r))) &&
+        lat >= q.lat_lo && lat <= q.lat_hi &&
+        (wraps ? (lon >= q.lon_lo || lon <= q.lon_hi) : (lon >= q.lon_lo && lon <= q.lon_hi))) {
+      *dist = near_haversine(p1, cos_p1, q.lon, lat, lon);
+      hit = *dist <= q.radius_m;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {                                   // publish the round's count, reserve its range
-      const uint32_t m = s_n < NEAR_CHUNK ? s_n : NEAR_CHUNK; // at most one match per row of the chunk
-      s_cnt = m;
-      s_n = 0;
-      if (m) s_base = atomicAdd(&counters[0], m);
-    }
-    __syncthreads();                                          // s_cnt stays as it is until the next round's publish
-    const uint32_t n = s_cnt;
-    if (n == 0) continue;                                     // the whole workgroup
-    const int64_t base = s_base;
-    for (uint32_t i = threadIdx.x; i < n; i += BLK) {
-      const int64_t pos = base + i;
-      if (pos < cap) { out_rows[pos] = s_rows[i]; out_dist[pos] = s_dist[i]; }
-    }
-    __syncthreads();                                          // the stage is free for the next round
-  }
+    n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
+    n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
+    return hit;
+  });
   if (lane_id() == 0) {
     if (n_cand) atomicAdd(&counters[1], n_cand);
     if (n_bad) atomicAdd(&counters[2], n_bad);
@@ -2119,6 +2125,7 @@ __global__ void k_reject_refs(const SwEventRec* __restrict__ work, const uint32_
   }
 }
 
+// ============================================================================ C ABI
 extern "C" {
 
 int sw_reject_refs(const SwEngineArgs* ap, const uint8_t* raw, const uint32_t* msg_off, int64_t n_msgs, uint32_t* out,
@@ -2470,14 +2477,11 @@ __global__ void k_pip_batch(const double* pts, int64_t n_pts, const double* vtx,
   }
 }
 
-int sw_store_filter(const uint8_t* etype, const int32_t* asg, const int64_t* date, int64_t n_rows, int32_t et,
-                    const uint32_t* bits, int64_t n_asg, int64_t lo, int64_t hi, uint32_t* out_rows, int64_t cap,
-                    uint32_t* n_match, hipStream_t s) {
+int sw_store_filter(const SwRingView* v, int32_t et, uint32_t* out_rows, int64_t cap, uint32_t* n_match, hipStream_t s) {
   hipError_t e = hipMemsetAsync(n_match, 0, sizeof(uint32_t), s);
   if (e != hipSuccess) return (int)e;
-  if (n_rows > 0)
-    k_store_filter<<<grid_for(n_rows), BLK, 0, s>>>(etype, asg, date, n_rows, et, bits, n_asg, lo, hi, out_rows, cap,
-                                                    n_match);
+  if (v->n_rows > 0)
+    k_store_filter<<<grid_for((v->n_rows + STAGE_U - 1) / STAGE_U), BLK, 0, s>>>(*v, (uint8_t)et, out_rows, cap, n_match);
   return (int)hipGetLastError();
 }
 
@@ -2486,7 +2490,7 @@ int sw_store_filter(const uint8_t* etype, const int32_t* asg, const int64_t* dat
 int sw_store_series_count(const SwSeriesQuery* q, uint32_t* sums, uint32_t* counters, hipStream_t s) {
   if (q->n_names < 1 || q->n_names > SW_SERIES_MAX_NAMES || q->bucket_ms < 1 || q->n_buckets < 1 ||
       q->n_names * q->n_buckets > SW_SERIES_MAX_CELLS || q->grid < 1 || q->rounds < 1 ||
-      q->grid * WAVES * q->rounds * 64 < q->n_rows)
+      q->grid * WAVES * q->rounds * 64 < q->ring.n_rows)
     return (int)hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(uint32_t), s);
   if (e != hipSuccess) return (int)e;
@@ -2524,16 +2528,17 @@ int sw_store_near(const SwNearQuery* q, uint32_t* out_rows, double* out_dist, in
                   hipStream_t s) {
   const bool centre = fabs(q->lat) <= 90.0 && fabs(q->lon) <= 180.0 && q->radius_m >= 0.0 && q->radius_m <= 1.0e7;
   const bool box = q->lat_lo <= q->lat_hi && fabs(q->lon_lo) <= 180.0 && fabs(q->lon_hi) <= 180.0;
-  if (!centre || !box || q->start > q->end || q->n_rows < 1 || q->n_rows > ((int64_t)1 << 32) || q->n_asg < 1 ||
-      cap < 1 || q->head < 0 || q->head >= q->n_rows || (q->latest && (!q->best_date || !q->best_seq)))
+  const SwRingView& v = q->ring;
+  if (!centre || !box || v.start > v.end || v.n_rows < 1 || v.n_rows > ((int64_t)1 << 32) || v.n_asg < 1 || cap < 1 ||
+      v.head < 0 || v.head >= v.n_rows || (q->latest && (!q->best_date || !q->best_seq)))
     return (int)hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(counters, 0, 3 * sizeof(uint32_t), s);
   if (e != hipSuccess) return (int)e;
   if (q->latest) {
-    k_near_best<0><<<grid_for(q->n_rows), BLK, 0, s>>>(*q);
-    k_near_best<1><<<grid_for(q->n_rows), BLK, 0, s>>>(*q);
+    k_near_best<0><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
+    k_near_best<1><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
   }
-  k_near_filter<<<grid_for((q->n_rows + NEAR_U - 1) / NEAR_U), BLK, 0, s>>>(*q, out_rows, out_dist, cap, counters);
+  k_near_filter<<<grid_for((v.n_rows + STAGE_U - 1) / STAGE_U), BLK, 0, s>>>(*q, out_rows, out_dist, cap, counters);
   return (int)hipGetLastError();
 }
 
@@ -2666,6 +2671,8 @@ int sw_abi_sizes(int64_t* out) {
   out[9] = sizeof(SwStrRef);
   out[10] = sizeof(SwStepSnapshot);
   out[11] = sizeof(SwNearQuery);
+  out[12] = sizeof(SwRingView);
+  out[13] = sizeof(SwSeriesQuery);
   return 0;
 }
 

@@ -288,42 +288,43 @@ static_assert(sizeof(SwSeriesCell) == 80, "SwSeriesCell is ten 8-byte words");
 #define SW_SERIES_MAX_NAMES 64
 #define SW_SERIES_MAX_CELLS 65536
 
-// A bucketed-series query (sw_store_series_count / sw_store_series): every field 8 bytes, so the host
-// builds it as an int64 array (SERIES_QUERY in sitewhere_amd/models/columnar.py names the words).
-typedef struct SwSeriesQuery {
+// The event ring as a hot-store query sees it, with the row test every such query shares (ring_row_test
+// in csrc/hip/swgpu.hip): rows of one event type whose assignment is in the bitmap and whose date lies
+// in [start, end].  Every field 8 bytes, so the host builds it as int64 words (RING_QUERY in
+// sitewhere_amd/models/columnar.py names them); the queries below begin with it and add their own.
+typedef struct SwRingView {
   const uint8_t* etype;        // ring columns
   const int32_t* asg;
   const int64_t* date;
-  const uint64_t* name;
-  const double* v0;
   int64_t n_rows;              // ring rows in use
   int64_t seq0;                // store sequence of ring row `head` (0 until the ring wraps)
   int64_t head;                // oldest ring row (0 until the ring wraps)
   const uint32_t* bits;        // assignment bitmap
   int64_t n_asg;               // its bits
+  int64_t start, end;          // date range, both ends included
+} SwRingView;
+static_assert(sizeof(SwRingView) == 80, "SwRingView is ten 8-byte words");
+
+// A bucketed-series query (sw_store_series_count / sw_store_series; SERIES_QUERY names the words).
+typedef struct SwSeriesQuery {
+  SwRingView ring;
+  const uint64_t* name;        // ring columns
+  const double* v0;
   const uint64_t* names;       // [n_names] measurement-name hashes
   int64_t n_names;
-  int64_t start, end, bucket_ms, n_buckets;
+  int64_t bucket_ms, n_buckets;
   int64_t rounds;              // 64-row rounds per wave of the two filter passes
   int64_t grid;                // their workgroups: the ring is cut into grid * 4 wave chunks
 } SwSeriesQuery;
+static_assert(sizeof(SwSeriesQuery) == 144, "SwSeriesQuery is 18 8-byte words");
 
-// A locations-near query (sw_store_near_best / sw_store_near): every field 8 bytes, so the host builds
-// it as an int64 array, the doubles by their bits (NEAR_QUERY in sitewhere_amd/models/columnar.py names
-// the words).  The box is the host's conservative cover of the cap (pipeline/near.py: near_box), in
+// A locations-near query (sw_store_near; NEAR_QUERY names the words, the doubles written by their
+// bits).  The box is the host's conservative cover of the cap (pipeline/near.py: near_box), in
 // degrees; lon_lo > lon_hi: the longitude interval wraps across +-180.
 typedef struct SwNearQuery {
-  const uint8_t* etype;        // ring columns
-  const int32_t* asg;
-  const int64_t* date;
-  const double* v0;            // latitude
+  SwRingView ring;             // ring.n_asg is also the entries of the two tables below
+  const double* v0;            // ring columns: latitude
   const double* v1;            // longitude
-  int64_t n_rows;              // ring rows in use
-  int64_t seq0;                // store sequence of ring row `head` (0 until the ring wraps)
-  int64_t head;                // oldest ring row (0 until the ring wraps)
-  const uint32_t* bits;        // assignment bitmap
-  int64_t n_asg;               // its bits, and the entries of the two tables below
-  int64_t start, end;
   double lat, lon, radius_m;   // centre (degrees) and radius
   double lat_lo, lat_hi, lon_lo, lon_hi;
   int64_t latest;              // 1: keep a row only if it is its assignment's newest valid candidate

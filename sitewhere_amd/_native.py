@@ -309,8 +309,7 @@ def gpu():
         _proto(lib, "sw_phase_unpack", c_int32, P, P)
         _proto(lib, "sw_phase_process", c_int32, P, P, P)
         _proto(lib, "sw_pip_batch", c_int32, P, c_int64, P, P, c_int64, P, P)
-        _proto(lib, "sw_store_filter", c_int32, P, P, P, c_int64, c_int32, P, c_int64, c_int64, c_int64, P, c_int64,
-               P, P)
+        _proto(lib, "sw_store_filter", c_int32, P, c_int32, P, c_int64, P, P)
         _proto(lib, "sw_store_series_count", c_int32, P, P, P, P)
         _proto(lib, "sw_store_series", c_int32, P, P, P, c_int64, P, P, c_int64, P, P, P, P, P)
         _proto(lib, "sw_store_near", c_int32, P, P, P, c_int64, P, P)

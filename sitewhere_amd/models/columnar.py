@@ -135,13 +135,14 @@ SERIES_CELL = np.dtype([
 assert SERIES_CELL.itemsize == 80
 SERIES_MAX_NAMES = 64          # SW_SERIES_MAX_NAMES
 SERIES_MAX_CELLS = 65536       # SW_SERIES_MAX_CELLS
+# The int64 words of the ring view every hot-store query begins with (SwRingView in swengine.h), in order.
+RING_QUERY = ("etype", "asg", "date", "n_rows", "seq0", "head", "bits", "n_asg", "start", "end")
 # The int64 words of a series query (SwSeriesQuery in swengine.h), in order.
-SERIES_QUERY = ("etype", "asg", "date", "name", "v0", "n_rows", "seq0", "head", "bits", "n_asg", "names", "n_names",
-                "start", "end", "bucket_ms", "n_buckets", "rounds", "grid")
+SERIES_QUERY = RING_QUERY + ("name", "v0", "names", "n_names", "bucket_ms", "n_buckets", "rounds", "grid")
 # The 8-byte words of a locations-near query (SwNearQuery in swengine.h), in order; NEAR_QUERY_F64 are
 # the doubles among them (written by their bits).
-NEAR_QUERY = ("etype", "asg", "date", "v0", "v1", "n_rows", "seq0", "head", "bits", "n_asg", "start", "end",
-              "lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "latest", "best_date", "best_seq")
+NEAR_QUERY = RING_QUERY + ("v0", "v1", "lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "latest",
+                           "best_date", "best_seq")
 NEAR_QUERY_F64 = ("lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi")
 
 # Durable-block encoder state (u64 words): the result words follow the max_pages look-back words

@@ -653,52 +653,14 @@ class CpuInboundEngine(EngineBase):
             "alerts": al,
         }
 
-    def query_store(self, event_type, asg_idx, start=None, end=None, page_number=1, page_size=100):
+    def _ring_candidates(self, event_type, asg_idx, start, end):
+        """(ring rows, their dates, their store sequences) of the rows of ``event_type`` whose assignment
+        is in ``asg_idx`` (None: every assignment) and whose date lies in [start, end] (None: that side
+        open): the row test of every hot-store query."""
         n = min(self.cursor, self.cfg.store_cap)
         s = self.store
+        d = s["date"][:n]
         m = s["etype"][:n] == event_type
-        m &= np.isin(s["asg"][:n], np.asarray(list(asg_idx), np.int32))
-        d = s["date"][:n]
-        if start is not None:
-            m &= d >= start
-        if end is not None:
-            m &= d <= end
-        rows = np.nonzero(m)[0]
-        seq = self._row_seq(rows.astype(np.int64), self.cursor)
-        order = np.lexsort((-seq, -d[rows]))
-        lo, hi = self._window(page_number, page_size, len(rows))
-        page = rows[order[lo:hi]]
-        cols = {k: v[page] for k, v in s.items()}
-        return len(rows), cols, seq[order[lo:hi]] * self.world + self.rank
-
-    def aggregate_store(self, asg_idx, name_hashes, start, end, bucket_ms):
-        """The oracle of the MI355X series kernels: a numpy filter, then ``series.bucket_series``."""
-        from .series import bucket_series, check_series_args
-        names, n_buckets = check_series_args(name_hashes, start, end, bucket_ms)
-        n = min(self.cursor, self.cfg.store_cap)
-        s = self.store
-        d = s["date"][:n]
-        m = (s["etype"][:n] == EV_MEASUREMENT) & np.isin(s["asg"][:n], np.asarray(list(asg_idx), np.int32))
-        m &= (d >= start) & (d <= end) & np.isin(s["name"][:n], np.asarray(names, np.uint64))
-        rows = np.nonzero(m)[0]
-        pos = {h: i for i, h in enumerate(names)}
-        idx = np.fromiter((pos[int(h)] for h in s["name"][rows]), np.int64, len(rows))
-        eids = self._row_seq(rows.astype(np.int64), self.cursor) * self.world + self.rank
-        cells, n_nan = bucket_series(idx, d[rows], eids, s["v0"][rows], int(start), int(bucket_ms), len(names), n_buckets)
-        wrapped = self.cursor > self.cfg.store_cap
-        hot = int(s["recv"][self.cursor % self.cfg.store_cap]) if wrapped else None
-        return cells, {"rows": len(rows) - n_nan, "nan": n_nan, "hot_since": hot}
-
-    def near_store(self, lat, lon, radius_m, asg_idx=None, start=None, end=None, latest=False, order="date",
-                   page_number=1, page_size=100):
-        """The oracle of the MI355X near kernels: a numpy filter, then ``near.near_select`` over every
-        candidate (no bounding-box prefilter)."""
-        from .near import check_near_args, near_select
-        lat, lon, radius_m = check_near_args(lat, lon, radius_m, start, end, order)
-        n = min(self.cursor, self.cfg.store_cap)
-        s = self.store
-        d = s["date"][:n]
-        m = s["etype"][:n] == EV_LOCATION
         if asg_idx is not None:
             m &= np.isin(s["asg"][:n], np.asarray(list(asg_idx), np.int32))
         if start is not None:
@@ -706,15 +668,44 @@ class CpuInboundEngine(EngineBase):
         if end is not None:
             m &= d <= end
         rows = np.nonzero(m)[0]
-        seq = self._row_seq(rows.astype(np.int64), self.cursor)
-        sel, dist, n_invalid = near_select(s["asg"][rows], d[rows], seq, s["v0"][rows], s["v1"][rows], lat, lon,
+        return rows, d[rows], self._row_seq(rows.astype(np.int64), self.cursor)
+
+    def query_store(self, event_type, asg_idx, start=None, end=None, page_number=1, page_size=100):
+        rows, d, seq = self._ring_candidates(event_type, asg_idx, start, end)
+        order = np.lexsort((-seq, -d))
+        lo, hi = self._window(page_number, page_size, len(rows))
+        page = rows[order[lo:hi]]
+        cols = {k: v[page] for k, v in self.store.items()}
+        return len(rows), cols, seq[order[lo:hi]] * self.world + self.rank
+
+    def aggregate_store(self, asg_idx, name_hashes, start, end, bucket_ms):
+        """The oracle of the MI355X series kernels: a numpy filter, then ``series.bucket_series``."""
+        from .series import bucket_series, check_series_args
+        names, n_buckets = check_series_args(name_hashes, start, end, bucket_ms)
+        s = self.store
+        rows, d, seq = self._ring_candidates(EV_MEASUREMENT, asg_idx, start, end)
+        named = np.isin(s["name"][rows], np.asarray(names, np.uint64))
+        rows, d, seq = rows[named], d[named], seq[named]
+        pos = {h: i for i, h in enumerate(names)}
+        idx = np.fromiter((pos[int(h)] for h in s["name"][rows]), np.int64, len(rows))
+        cells, n_nan = bucket_series(idx, d, seq * self.world + self.rank, s["v0"][rows], int(start), int(bucket_ms),
+                                     len(names), n_buckets)
+        return cells, {"rows": len(rows) - n_nan, "nan": n_nan, "hot_since": self._hot_since(self.cursor)}
+
+    def near_store(self, lat, lon, radius_m, asg_idx=None, start=None, end=None, latest=False, order="date",
+                   page_number=1, page_size=100):
+        """The oracle of the MI355X near kernels: a numpy filter, then ``near.near_select`` over every
+        candidate (no bounding-box prefilter)."""
+        from .near import check_near_args, near_select
+        lat, lon, radius_m = check_near_args(lat, lon, radius_m, start, end, order)
+        s = self.store
+        rows, d, seq = self._ring_candidates(EV_LOCATION, asg_idx, start, end)
+        sel, dist, n_invalid = near_select(s["asg"][rows], d, seq, s["v0"][rows], s["v1"][rows], lat, lon,
                                            radius_m, bool(latest), order)
         lo, hi = self._window(page_number, page_size, len(sel))
         page = rows[sel[lo:hi]]
         cols = {k: v[page] for k, v in s.items()}
-        wrapped = self.cursor > self.cfg.store_cap
-        hot = int(s["recv"][self.cursor % self.cfg.store_cap]) if wrapped else None
-        info = {"candidates": len(rows), "invalid": n_invalid, "hot_since": hot}
+        info = {"candidates": len(rows), "invalid": n_invalid, "hot_since": self._hot_since(self.cursor)}
         return len(sel), cols, seq[sel[lo:hi]] * self.world + self.rank, dist[lo:hi], info
 
     def intern_table(self) -> dict:

@@ -482,6 +482,11 @@ class EngineBase:
             return rows
         return (cursor - cap) + (rows - (cursor % cap)) % cap
 
+    def _hot_since(self, cursor: int):
+        """Received date of the oldest ring row once the ring has wrapped, else None."""
+        cap = self.cfg.store_cap
+        return int(self.store["recv"][cursor % cap]) if cursor > cap else None
+
     # ------------------------------------------------------------------ durable blocks
     def encode_block(self, now_ms: int, res: StepResult | None = None, slot: int | None = None,
                      boot: int = 0) -> np.ndarray:

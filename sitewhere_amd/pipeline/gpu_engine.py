@@ -15,6 +15,7 @@ on three streams.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import time
 
@@ -22,9 +23,10 @@ import numpy as np
 import torch
 
 from .._native import gpu_gil as gpu_lib
-from ..models.columnar import (EVENT_REC, N_STATS, OUT_REC, NAME_REF, OUT_REC_SIZE, SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK,
-                               SC_N_OUT, SC_N_RECS, SC_N_REJ, SC_N_RULE, SC_N_WORK, SC_NAMES, SC_OVERFLOW,
-                               SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC)
+from ..models.columnar import (EVENT_REC, N_STATS, NEAR_QUERY, NEAR_QUERY_F64, OUT_REC, NAME_REF, OUT_REC_SIZE, RING_QUERY,
+                               SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK, SC_N_OUT, SC_N_RECS, SC_N_REJ, SC_N_RULE, SC_N_WORK,
+                               SC_NAMES, SC_OVERFLOW, SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, SERIES_CELL, SERIES_QUERY,
+                               ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC)
 from ..ops.engine_abi import SwEngineArgs
 from .config import EngineConfig
 from .bus_io import host_view
@@ -32,6 +34,7 @@ from .engine_base import EngineBase, StepResult
 from .pinned_pool import PinnedPool
 
 _ALIGN = 64
+_I64 = np.iinfo(np.int64)
 
 
 def _ptr(t: torch.Tensor) -> int:
@@ -388,6 +391,7 @@ class GpuInboundEngine(EngineBase):
         self._segs, self._aux_dev, self._rej_refs = {}, {}, {}      # per outbound slot
         self._ix_scratch = None
         self._carry_seen = None                # re-key carry of the pipelined runner's last snapshot
+        self._ring_bufs = {}                   # hot-store queries' device buffers: query -> name -> tensor
         from ..persistence.segments import max_block_bytes
         self._pins = {"rows": PinnedPool(out_cap * OUT_REC_SIZE, self.PIN_POOL, self.PIN_SPILL),
                       "blocks": PinnedPool(max_block_bytes(out_cap), self.PIN_POOL_BLOCKS, self.PIN_SPILL)}
@@ -1282,42 +1286,73 @@ class GpuInboundEngine(EngineBase):
             return self._query_store(event_type, asg_idx, start, end, page_number, page_size)
 
     def _asg_bitmap(self, asg_idx):
-        """An assignment set as a bitmap over ``max_assignments`` in HBM (the hot-store kernels' set test)."""
+        """An assignment set (None: every assignment) as a bitmap over ``max_assignments`` in HBM."""
         nbits = self.cfg.max_assignments
+        if asg_idx is None:
+            return torch.full(((nbits + 31) // 32,), -1, dtype=torch.int32, device=self.device)
         words = np.zeros((nbits + 31) // 32, np.uint32)
         a = np.asarray(list(asg_idx), np.int64)
         a = a[(a >= 0) & (a < nbits)]
         np.bitwise_or.at(words, a >> 5, (np.uint32(1) << (a & 31).astype(np.uint32)))
         return torch.from_numpy(words.view(np.int32)).to(self.device)
 
-    def _query_store(self, event_type, asg_idx, start, end, page_number, page_size):
+    def _ring_view(self, asg_idx, start, end):
+        """What every hot-store query starts from, read under the engine lock: (cursor, ``RING_QUERY``'s words
+        by name, the bitmap tensor they point into; none for an empty ring: nothing is allocated or
+        launched).  ``start`` / ``end`` None: that side open."""
         cur = self.cursor
-        n = min(cur, self.cfg.store_cap)
-        nbits = self.cfg.max_assignments
-        bits = self._asg_bitmap(asg_idx)
-        if getattr(self, "_q_rows", None) is None or self._q_rows.numel() < max(n, 1):
-            self._q_rows = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
-            self._q_n = torch.zeros(1, dtype=torch.int32, device=self.device)
-        i64 = np.iinfo(np.int64)
+        ring = self.cfg.store_cap
+        n = min(cur, ring)
         st = self.store
-        _chk(self.lib.sw_store_filter(_ptr(st["etype"]), _ptr(st["asg"]), _ptr(st["date"]), n, int(event_type),
-                                      _ptr(bits), nbits, i64.min if start is None else int(start),
-                                      i64.max if end is None else int(end), _ptr(self._q_rows), self._q_rows.numel(),
-                                      _ptr(self._q_n), self._stream()), "sw_store_filter")
-        total = int(self._q_n.item())
-        rows = self._q_rows[:total].long()
+        bits = self._asg_bitmap(asg_idx) if n else None
+        return cur, dict(etype=_ptr(st["etype"]), asg=_ptr(st["asg"]), date=_ptr(st["date"]), n_rows=n, seq0=cur - n,
+                         head=cur % ring if cur > ring else 0, bits=_ptr(bits) if n else 0, n_asg=self.cfg.max_assignments,
+                         start=_I64.min if start is None else int(start), end=_I64.max if end is None else int(end)), bits
+
+    @staticmethod
+    def _query_words(names, f64, vals):
+        """A query struct of 8-byte words as an int64 array; the words named in ``f64`` are doubles, by their bits."""
+        q = np.array([0 if k in f64 else vals[k] for k in names], np.int64)
+        if f64:
+            q.view(np.float64)[[names.index(k) for k in f64]] = [vals[k] for k in f64]
+        return q
+
+    def _ring_buf(self, query: str, key: str, n: int, dtype=torch.int32):
+        """A device buffer of at least ``n`` elements that ``query`` keeps from call to call (the engine
+        lock serialises the queries; each has its own keys, so none is handed another's buffer)."""
+        bufs = self._ring_bufs.setdefault(query, {})
+        b = bufs.get(key)
+        if b is None or b.numel() < n:
+            b = bufs[key] = torch.empty(n, dtype=dtype, device=self.device)
+        return b
+
+    def _order_page(self, rows, cur, page_number, page_size, dist=None, by_distance=False):
+        """Order a match set (ring rows, int64, on the device; ``dist`` beside them) and fetch one page:
+        (columns, event ids, distances or None).  Stable sorts, least significant key first: event id
+        desc, date desc (newest first, ties by latest id), then distance asc when ``by_distance``."""
+        st = self.store
         seq = self._row_seq(rows, cur)
-        # newest first, ties by latest id: stable sort by seq desc, then stable by date desc
-        o1 = torch.sort(seq, descending=True, stable=True).indices
-        dates = st["date"][rows[o1]]
-        o2 = torch.sort(dates, descending=True, stable=True).indices
-        lo, hi = self._window(page_number, page_size, total)
-        sel = o1[o2[lo:hi]]
+        o = torch.sort(seq, descending=True, stable=True).indices
+        o2 = torch.sort(st["date"][rows[o]], descending=True, stable=True).indices
+        if by_distance:
+            o = o[o2]
+            o2 = torch.sort(dist[o], stable=True).indices
+        lo, hi = self._window(page_number, page_size, len(rows))
+        sel = o[o2[lo:hi]]
         page = rows[sel]
-        cols = {k: v[page].cpu().numpy() for k, v in st.items()}
-        for k in ("name", "alt", "aux"):
-            cols[k] = cols[k].view(np.uint64)
-        return total, cols, seq[sel].cpu().numpy() * self.world + self.rank
+        cols = self._u64_cols({k: v[page].cpu().numpy() for k, v in st.items()})
+        return cols, seq[sel].cpu().numpy() * self.world + self.rank, None if dist is None else dist[sel].cpu().numpy()
+
+    def _query_store(self, event_type, asg_idx, start, end, page_number, page_size):
+        cur, view, bits = self._ring_view(asg_idx, start, end)
+        rows = self._ring_buf("query", "rows", max(view["n_rows"], 1))          # ring-sized: any match count fits
+        n_match = self._ring_buf("query", "n", 1)
+        q = self._query_words(RING_QUERY, (), view)
+        _chk(self.lib.sw_store_filter(q.ctypes.data, int(event_type), _ptr(rows), rows.numel(), _ptr(n_match),
+                                      self._stream()), "sw_store_filter")
+        total = int(n_match.item())
+        cols, eids, _ = self._order_page(rows[:total].long(), cur, page_number, page_size)
+        return total, cols, eids
 
     def aggregate_store(self, asg_idx, name_hashes, start, end, bucket_ms):
         """Bucketed series on the MI355X (``sw_store_series``, csrc/hip/swgpu.hip): two filter passes
@@ -1331,38 +1366,24 @@ class GpuInboundEngine(EngineBase):
         with self._lock:
             return self._aggregate_store(asg_idx, names, int(start), int(end), int(bucket_ms), n_buckets)
 
-    def _series_buf(self, key: str, n: int, dtype=torch.int32, pool: str = "_s_bufs"):
-        bufs = self.__dict__.setdefault(pool, {})
-        b = bufs.get(key)
-        if b is None or b.numel() < n:
-            b = bufs[key] = torch.empty(n, dtype=dtype, device=self.device)
-        return b
-
     def _aggregate_store(self, asg_idx, names, start, end, bucket_ms, n_buckets):
-        from ..models.columnar import SERIES_CELL, SERIES_QUERY
-        cur = self.cursor
-        ring = self.cfg.store_cap
-        n = min(cur, ring)
         n_cells = len(names) * n_buckets
         info = {"rows": 0, "nan": 0, "hot_since": None}
+        cur, view, bits = self._ring_view(asg_idx, start, end)
+        n = view["n_rows"]
         if n == 0:
             return np.zeros((len(names), n_buckets), SERIES_CELL), info
+        info["hot_since"] = self._hot_since(cur)
         st = self.store
-        head = cur % ring if cur > ring else 0
-        if cur > ring:
-            info["hot_since"] = int(st["recv"][head].item())
-        nbits = self.cfg.max_assignments
-        bits = self._asg_bitmap(asg_idx)
+        buf = functools.partial(self._ring_buf, "series")
         nm = torch.from_numpy(np.asarray(names, np.uint64).view(np.int64)).to(self.device)
         # each wave of the two filter passes owns `rounds` runs of 64 ring rows, in at most 2048 workgroups
         rounds = max(1, -(-n // (256 * 2048)))
         grid = -(-n // (256 * rounds))
-        sums, counters = self._series_buf("sums", 4 * grid), self._series_buf("counters", 2)
-        q = dict(etype=_ptr(st["etype"]), asg=_ptr(st["asg"]), date=_ptr(st["date"]), name=_ptr(st["name"]),
-                 v0=_ptr(st["v0"]), n_rows=n, seq0=cur - n, head=head, bits=_ptr(bits), n_asg=nbits, names=_ptr(nm),
-                 n_names=len(names), start=start, end=end, bucket_ms=bucket_ms, n_buckets=n_buckets, rounds=rounds,
-                 grid=grid)
-        q = np.array([q[k] for k in SERIES_QUERY], np.int64)
+        sums, counters = buf("sums", 4 * grid), buf("counters", 2)
+        q = self._query_words(SERIES_QUERY, (), dict(view, name=_ptr(st["name"]), v0=_ptr(st["v0"]), names=_ptr(nm),
+                                                     n_names=len(names), bucket_ms=bucket_ms, n_buckets=n_buckets,
+                                                     rounds=rounds, grid=grid))
         stream = self._stream()
         _chk(self.lib.sw_store_series_count(q.ctypes.data, _ptr(sums), _ptr(counters), stream), "sw_store_series_count")
         n_match, n_nan = (int(x) for x in counters.cpu().numpy().view(np.uint32))
@@ -1372,11 +1393,11 @@ class GpuInboundEngine(EngineBase):
         # the sort sizes its grid by the capacity: keep it near the match count, not the ring size
         cap = -(-n_match // 4096) * 4096
         tiles = -(-n_match // 256)
-        keys, rows = self._series_buf("keys", 2 * cap), self._series_buf("rows", 2 * cap)
-        rstate = self._series_buf("rstate", int(self.lib.sw_radix_tmp_words(cap)))
-        carry = self._series_buf("carry", 2 * tiles * 10, torch.int64)
-        ckey = self._series_buf("ckey", 2 * tiles)
-        dcells = self._series_buf("cells", n_cells * 10, torch.int64)
+        keys, rows = buf("keys", 2 * cap), buf("rows", 2 * cap)
+        rstate = buf("rstate", int(self.lib.sw_radix_tmp_words(cap)))
+        carry = buf("carry", 2 * tiles * 10, torch.int64)
+        ckey = buf("ckey", 2 * tiles)
+        dcells = buf("cells", n_cells * 10, torch.int64)
         _chk(self.lib.sw_store_series(q.ctypes.data, _ptr(sums), _ptr(counters), n_match, _ptr(keys), _ptr(rows), cap,
                                       _ptr(rstate), _ptr(carry), _ptr(ckey), _ptr(dcells), stream), "sw_store_series")
         cells = dcells[:n_cells * 10].cpu().numpy().view(SERIES_CELL).reshape(len(names), n_buckets)
@@ -1403,45 +1424,29 @@ class GpuInboundEngine(EngineBase):
     _near_rows0 = 1 << 20          # first size of near_store's match buffers, in rows (12 B each)
 
     def _near_store(self, lat, lon, radius_m, asg_idx, start, end, latest, order, page_number, page_size):
-        from ..models.columnar import NEAR_QUERY, NEAR_QUERY_F64
         from .near import near_box
-        cur = self.cursor
-        ring = self.cfg.store_cap
-        n = min(cur, ring)
         st = self.store
         info = {"candidates": 0, "invalid": 0, "hot_since": None}
+        cur, view, bits = self._ring_view(asg_idx, start, end)
+        n, nbits = view["n_rows"], view["n_asg"]
         if n == 0:
             cols = {k: torch.empty(0, dtype=v.dtype).numpy() for k, v in st.items()}       # host tensors: no launch
             return 0, self._u64_cols(cols), np.zeros(0, np.int64), np.zeros(0, np.float64), info
-        head = cur % ring if cur > ring else 0
-        if cur > ring:
-            info["hot_since"] = int(st["recv"][head].item())
-        nbits = self.cfg.max_assignments
-        if asg_idx is None:
-            bits = torch.full(((nbits + 31) // 32,), -1, dtype=torch.int32, device=self.device)
-        else:
-            bits = self._asg_bitmap(asg_idx)
-        buf = lambda key, m, dtype=torch.int32: self._series_buf(key, m, dtype, pool="_n_bufs")  # noqa: E731
-        i64 = np.iinfo(np.int64)
+        info["hot_since"] = self._hot_since(cur)
+        buf = functools.partial(self._ring_buf, "near")
         best = None
         if latest:
             best = buf("best", 2 * nbits, torch.int64)
-            best[:2 * nbits].fill_(i64.min)
+            best[:2 * nbits].fill_(_I64.min)
         lat_lo, lat_hi, lon_lo, lon_hi = near_box(lat, lon, radius_m)
-        vals = dict(etype=_ptr(st["etype"]), asg=_ptr(st["asg"]), date=_ptr(st["date"]), v0=_ptr(st["v0"]),
-                    v1=_ptr(st["v1"]), n_rows=n, seq0=cur - n, head=head, bits=_ptr(bits), n_asg=nbits,
-                    start=i64.min if start is None else int(start), end=i64.max if end is None else int(end),
-                    lat=lat, lon=lon, radius_m=radius_m, lat_lo=lat_lo, lat_hi=lat_hi, lon_lo=lon_lo, lon_hi=lon_hi,
-                    latest=int(latest), best_date=_ptr(best) if latest else 0,
-                    best_seq=_ptr(best) + 8 * nbits if latest else 0)
-        q = np.zeros(len(NEAR_QUERY), np.int64)
-        qf = q.view(np.float64)
-        for i, k in enumerate(NEAR_QUERY):
-            (qf if k in NEAR_QUERY_F64 else q)[i] = vals[k]
+        q = self._query_words(NEAR_QUERY, NEAR_QUERY_F64, dict(
+            view, v0=_ptr(st["v0"]), v1=_ptr(st["v1"]), lat=lat, lon=lon, radius_m=radius_m, lat_lo=lat_lo, lat_hi=lat_hi,
+            lon_lo=lon_lo, lon_hi=lon_hi, latest=int(latest), best_date=_ptr(best) if latest else 0,
+            best_seq=_ptr(best) + 8 * nbits if latest else 0))
         counters = buf("counters", 3)
         # the match buffers start at _near_rows0 rows (or what an earlier query grew them to); when that is
         # short they grow to the match count and the pass is repeated
-        held = self.__dict__.get("_n_bufs", {}).get("rows")
+        held = self._ring_bufs["near"].get("rows")
         cap = min(n, max(self._near_rows0, 0 if held is None else held.numel()))
         stream = self._stream()
         while True:
@@ -1453,20 +1458,10 @@ class GpuInboundEngine(EngineBase):
                 break
             cap = total
             if latest:
-                best[:2 * nbits].fill_(i64.min)
-        rows = rows[:total].long() & 0xFFFFFFFF
-        dist = dist[:total]
-        seq = self._row_seq(rows, cur)
-        # stable sorts, least significant key first: event id desc, date desc, then distance asc
-        o = torch.sort(seq, descending=True, stable=True).indices
-        o = o[torch.sort(st["date"][rows[o]], descending=True, stable=True).indices]
-        if order == "distance":
-            o = o[torch.sort(dist[o], stable=True).indices]
-        lo, hi = self._window(page_number, page_size, total)
-        sel = o[lo:hi]
-        page = rows[sel]
-        cols = self._u64_cols({k: v[page].cpu().numpy() for k, v in st.items()})
-        return total, cols, seq[sel].cpu().numpy() * self.world + self.rank, dist[sel].cpu().numpy(), info
+                best[:2 * nbits].fill_(_I64.min)
+        cols, eids, dist = self._order_page(rows[:total].long() & 0xFFFFFFFF, cur, page_number, page_size, dist[:total],
+                                            order == "distance")
+        return total, cols, eids, dist, info
 
     @staticmethod
     def _u64_cols(cols):
@@ -1481,9 +1476,7 @@ class GpuInboundEngine(EngineBase):
         idx = torch.arange(n, device=self.device)
         if cur > cap:
             idx = (idx + cur % cap) % cap
-        cols = {k: v[idx].cpu().numpy() for k, v in self.store.items()}
-        for k in ("name", "alt", "aux"):
-            cols[k] = cols[k].view(np.uint64)
+        cols = self._u64_cols({k: v[idx].cpu().numpy() for k, v in self.store.items()})
         return cols, (np.arange(cur - n, cur) * self.world + self.rank)
 
     # ------------------------------------------------------------------ checkpoint / resume

@@ -70,3 +70,23 @@ def test_step_snapshot_matches_header():
            for k in dt.names]
     assert got == fields
     assert dt.itemsize == off == 128
+
+
+def test_ring_view_heads_the_hot_store_queries():
+    """RING_QUERY against SwRingView, field by field, and as the head of the two query word lists."""
+    from sitewhere_amd.models.columnar import NEAR_QUERY, RING_QUERY, SERIES_QUERY
+    text = re.sub(r"//[^\n]*", "", HEADER.read_text())
+    body = re.search(r"typedef struct SwRingView \{(.*?)\} SwRingView;", text, re.S).group(1)
+    fields = []
+    for decl in body.split(";"):
+        if decl.strip():
+            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(\w+(?:\s*,\s*\w+)*)", decl.strip())
+            assert m, f"unparsed declaration in SwRingView: {decl!r}"
+            assert m.group(2) or m.group(1) == "int64_t"           # every field 8 bytes
+            fields += [f.strip() for f in m.group(3).split(",")]
+    assert tuple(fields) == RING_QUERY
+    assert "static_assert(sizeof(SwRingView) == %d" % (8 * len(RING_QUERY)) in text
+    for words, name, size in ((SERIES_QUERY, "SwSeriesQuery", 144), (NEAR_QUERY, "SwNearQuery", 176)):
+        assert words[:len(RING_QUERY)] == RING_QUERY and len(set(words)) == len(words)
+        assert re.search(r"typedef struct %s \{\s*SwRingView \w+;" % name, text)       # the view is the first member
+        assert 8 * len(words) == size and "static_assert(sizeof(%s) == %d" % (name, size) in text

@@ -241,6 +241,39 @@ def test_hot_store_query_kernel_matches_cpu_oracle():
             assert np.array_equal(pg[k], pc[k]), k
 
 
+def test_hot_store_query_dense_partial_chunk_stray_indices_and_empty():
+    """query_store against the CPU oracle, all exact, where the match compactor can go wrong: an
+    unwrapped ring whose row count is a multiple of neither the wave (64) nor the 1024-row chunk, with
+    most rows of every chunk matching; an assignment set with indices outside [0, max_assignments),
+    which are ignored; a query nothing matches; a ring no step has written to."""
+    from sitewhere_amd.models.columnar import EV_ALERT, EV_MEASUREMENT
+    g = GpuInboundEngine(small_cfg(store_cap=1 << 12), device="cuda:0")
+    c = CpuInboundEngine(small_cfg(store_cap=1 << 12))
+
+    def same(*q):
+        (tg, pg, eg), (tc, pc, ec) = g.query_store(*q), c.query_store(*q)
+        assert tg == tc and np.array_equal(eg, ec)
+        for k in ("date", "asg", "etype", "v0", "v1"):
+            assert np.array_equal(pg[k], pc[k]), k
+        return tg, len(eg)
+
+    every = list(range(g.cfg.max_assignments))
+    assert same(EV_MEASUREMENT, every, None, None, 1, 0) == (0, 0)            # no step yet: an empty page
+    for e in (g, c):
+        setup_fleet(e, n_dev=200)
+        raw, offs = fleet_batch(1500, seed=70, n_dev=200)
+        e.step(raw, offs, NOW, presence=False)
+    n = g.cursor
+    assert n == c.cursor and 2048 < n < g.cfg.store_cap and n % 64 and n % 1024      # two full chunks and a part
+    total, page = same(EV_MEASUREMENT, every, None, None, 1, 0)
+    assert total == page and 2 * total > n
+    stray = [-1, -4097, 3, 150, g.cfg.max_assignments, g.cfg.max_assignments + 31, 1 << 20]
+    assert same(EV_MEASUREMENT, stray, None, None, 1, 0) == same(EV_MEASUREMENT, [3, 150], None, None, 1, 0)
+    assert same(EV_MEASUREMENT, stray, None, None, 1, 0)[0] > 0
+    assert same(EV_MEASUREMENT, every, NOW + 10_000_000, None, 1, 0) == (0, 0)
+    assert same(EV_ALERT, [199 + 1000], None, None, 1, 10) == (0, 0)
+
+
 def test_overlapped_framed_steps_match_sync_oracle():
     """submit_framed / drain_framed (the service tenant's overlapped steps): batch k is returned when
     batch k+2 is submitted, from pinned zero-copy records.  Every result -- rows, rejects, learned

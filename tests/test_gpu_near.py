@@ -92,7 +92,7 @@ def test_hand_batch_partial_wave_antimeridian_pole_invalid_ties():
 def test_empty_ring_and_refused_arguments_launch_nothing():
     g = GpuInboundEngine(small_cfg())
     total, cols, eids, dist, info = g.near_store(*CENTRE, 1000.0, latest=True)     # cursor == 0: no buffer, no kernel
-    assert total == 0 and info == {"candidates": 0, "invalid": 0, "hot_since": None} and "_n_bufs" not in g.__dict__
+    assert total == 0 and info == {"candidates": 0, "invalid": 0, "hot_since": None} and "near" not in g._ring_bufs
     assert len(eids) == len(dist) == 0 and dist.dtype == np.float64 and cols["v0"].dtype == np.float64
     assert cols["name"].dtype == np.uint64 and all(len(v) == 0 for v in cols.values())
     fill_ring(g)
@@ -105,21 +105,21 @@ def test_empty_ring_and_refused_arguments_launch_nothing():
         g.near_store(0.0, 0.0, 1.0, start=NOW, end=NOW - 1)
     with pytest.raises(ValueError):
         g.near_store(0.0, 0.0, 1.0, order="nearest")
-    assert "_n_bufs" not in g.__dict__                 # nothing was allocated, so nothing was launched
+    assert "near" not in g._ring_bufs                # nothing was allocated, so nothing was launched
     # a query nothing matches: counted on the device, an empty page
     total, cols, eids, dist, info = g.near_store(-33.5, 95.5, 1000.0)
-    assert total == 0 and len(eids) == len(dist) == 0 and info["candidates"] > 0 and "_n_bufs" in g.__dict__
+    assert total == 0 and len(eids) == len(dist) == 0 and info["candidates"] > 0 and "near" in g._ring_bufs
 
 
 def test_match_buffers_grow_and_the_pass_repeats():
     g, c, _ = ring_pair(1 << 14)
     g._near_rows0 = 256                                # fewer rows than the 925 and 1914 matches below
     check(g, c, lat=CENTRE[0], lon=CENTRE[1], radius_m=60000.0, order="distance", page_size=0)
-    assert g._n_bufs["rows"].numel() == g._n_bufs["dist"].numel() == 925
+    assert g._ring_bufs["near"]["rows"].numel() == g._ring_bufs["near"]["dist"].numel() == 925
     check(g, c, lat=CENTRE[0], lon=CENTRE[1], radius_m=250000.0, latest=True, page_size=0)      # 180 rows: fits
-    assert g._n_bufs["rows"].numel() == 925
+    assert g._ring_bufs["near"]["rows"].numel() == 925
     check(g, c, lat=CENTRE[0], lon=CENTRE[1], radius_m=250000.0, page_size=0)
-    assert g._n_bufs["rows"].numel() == 1914
+    assert g._ring_bufs["near"]["rows"].numel() == 1914
 
 
 def test_abi_size_of_the_query():

@@ -71,7 +71,7 @@ def test_partial_wave_nan_signed_zeros_and_empty_ring():
     g, c = GpuInboundEngine(small_cfg()), CpuInboundEngine(small_cfg())
     query = ([1, 2], [hash64("temp"), hash64("hum")], NOW - 100, NOW - 71, 10)
     cells, info = g.aggregate_store(*query)                                   # cursor == 0: no kernel, zeroed cells
-    assert info == {"rows": 0, "nan": 0, "hot_since": None} and "_s_bufs" not in g.__dict__
+    assert info == {"rows": 0, "nan": 0, "hot_since": None} and "series" not in g._ring_bufs
     assert cells.shape == (2, 3) and not cells.tobytes().strip(b"\0")
     for e in (g, c):
         setup_fleet(e, n_dev=1000)
@@ -116,5 +116,5 @@ def test_argument_errors_launch_nothing():
                 (ALL, NAMES, NOW - 8192, NOW, 1)):
         with pytest.raises(ValueError):
             g.aggregate_store(*bad)
-    assert "_s_bufs" not in g.__dict__                 # nothing was allocated, so nothing was launched
+    assert "series" not in g._ring_bufs              # nothing was allocated, so nothing was launched
     assert g.aggregate_store(ALL, NAMES, NOW - 8191, NOW, 1)[0].size == 65536

@@ -186,6 +186,9 @@ def _struct_fields(name):
         if decl.strip():
             m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(.+)", decl.strip(), re.S)
             assert m, f"unparsed declaration in {name}: {decl!r}"
+            if m.group(1) == "SwRingView":                     # the shared head, by value: its words come first
+                fields += _struct_fields("SwRingView")[1]
+                continue
             for f in m.group(3).split(","):
                 fields.append((f.strip(), "ptr" if m.group(2) else m.group(1)))
     return text, fields
