@@ -1674,7 +1674,7 @@ __global__ void k_step_end(SwEngineArgs a, const uint32_t* n_rule_alerts) {
 }
 
 // ============================================================================ hot-store queries
-// What the three reads over the HBM event ring share, beside their view of it (SwRingView, swengine.h).
+// What the four reads over the HBM event ring share, beside their view of it (SwRingView, swengine.h).
 
 // Store sequence of ring row r: the ring's oldest row is `head`.
 __device__ __forceinline__ int64_t ring_seq(const SwRingView& v, int64_t r) {
@@ -1700,6 +1700,9 @@ __device__ __forceinline__ bool ring_row_test(const SwRingView& v, int64_t r, ui
 // atomic per wave that has any), then the workgroup reserves its output range with one global atomic
 // and copies the stage out.  One global atomic per wave instead was measured at 24 ms over a 2^27-row
 // ring when most waves have a match (2.1M atomics on one address; profiles/hot_near/README.md).
+// tail(push), if given, runs once per chunk after its rows were asked, every thread in step: what hit
+// set aside in the chunk (k_zone_filter's box hits) it decides there and stages with push(match, row,
+// dist), whole waves calling; at most one match per row of the chunk still.
 #define STAGE_U 4
 #define STAGE_CHUNK (BLK * STAGE_U)
 template <bool DIST> struct RingStageDist { double dist[STAGE_CHUNK]; };
@@ -1709,10 +1712,10 @@ template <bool DIST> struct RingStage : RingStageDist<DIST> {
   uint32_t n[2], base;          // matches staged in even / odd rounds; the round's place in the output
 };
 
-template <bool DIST, class Hit>
+template <bool DIST, class Hit, class Tail>
 __device__ __forceinline__ void ring_compact(int64_t n_rows, uint32_t* __restrict__ out_rows,
                                              double* __restrict__ out_dist, int64_t cap,
-                                             uint32_t* __restrict__ n_match, Hit hit) {
+                                             uint32_t* __restrict__ n_match, Hit hit, Tail tail) {
   __shared__ RingStage<DIST> st;
   // every thread runs the same number of rounds (the ballots need whole waves, the barriers the workgroup)
   const int64_t n_chunks = (n_rows + STAGE_CHUNK - 1) / STAGE_CHUNK;
@@ -1722,12 +1725,10 @@ __device__ __forceinline__ void ring_compact(int64_t n_rows, uint32_t* __restric
   for (int64_t it = 0; it < iters; ++it) {
     const int64_t row0 = ((int64_t)BID + it * gridDim.x) * STAGE_CHUNK;     // past the ring: no row passes
     uint32_t& staged = st.n[it & 1];
-    for (int u = 0; u < STAGE_U; ++u) {
-      const int64_t r = row0 + u * BLK + threadIdx.x;
-      double dist = 0.0;
-      const bool h = hit(r, &dist);
+    // a wave's matches into the stage: whole waves call it
+    auto push = [&](bool h, int64_t r, double dist) {
       const ull mask = __ballot(h);
-      if (!mask) continue;
+      if (!mask) return;
       uint32_t base = 0;
       if (lane_id() == 0) base = atomicAdd(&staged, (uint32_t)__popcll(mask));
       base = __shfl(base, 0, 64);
@@ -1738,7 +1739,14 @@ __device__ __forceinline__ void ring_compact(int64_t n_rows, uint32_t* __restric
           if constexpr (DIST) st.dist[pos] = dist;
         }
       }
+    };
+    for (int u = 0; u < STAGE_U; ++u) {
+      const int64_t r = row0 + u * BLK + threadIdx.x;
+      double dist = 0.0;
+      const bool h = hit(r, &dist);
+      push(h, r, dist);
     }
+    tail(push);
     __syncthreads();
     // the round's count: nobody adds to it again before the round after next, which lies behind the next
     // round's barrier, so every thread reads the same value; at most one match per row of the chunk
@@ -1757,6 +1765,13 @@ __device__ __forceinline__ void ring_compact(int64_t n_rows, uint32_t* __restric
     }
     __syncthreads();                                            // the stage is free for the next round
   }
+}
+
+template <bool DIST, class Hit>
+__device__ __forceinline__ void ring_compact(int64_t n_rows, uint32_t* __restrict__ out_rows,
+                                             double* __restrict__ out_dist, int64_t cap,
+                                             uint32_t* __restrict__ n_match, Hit hit) {
+  ring_compact<DIST>(n_rows, out_rows, out_dist, cap, n_match, hit, [](auto&) {});
 }
 
 // Event-management reads (DeviceEventManagement.list*ForIndex, EventManagementImpl.java): the rows that
@@ -1950,8 +1965,10 @@ __global__ __launch_bounds__(BLK) void k_series_carry(const SwSeriesCell* __rest
 // if it is that one.  No floating-point atomics.
 enum { NEAR_NO = 0, NEAR_INVALID = 1, NEAR_VALID = 2 };
 
-// The row's class; for a candidate (valid or not) *a, *d, *lat, *lon are its columns.
-__device__ __forceinline__ int near_candidate(const SwNearQuery& q, int64_t r, int32_t* a, int64_t* d, double* lat,
+// The row's class; for a candidate (valid or not) *a, *d, *lat, *lon are its columns.  Q: SwNearQuery or
+// SwZoneQuery (ring, v0, v1).
+template <class Q>
+__device__ __forceinline__ int near_candidate(const Q& q, int64_t r, int32_t* a, int64_t* d, double* lat,
                                               double* lon) {
   if (!ring_row_test(q.ring, r, (uint8_t)SW_EV_LOCATION, a, d)) return NEAR_NO;
   *lat = q.v0[r];
@@ -1973,9 +1990,10 @@ __device__ __forceinline__ double near_haversine(double p1, double cos_p1, doubl
 
 // PASS 0: best_date[a] = newest date among a's valid candidates; PASS 1: best_seq[a] = largest store
 // sequence among those at that date.  The plain read ahead of the atomic saves most atomics on a ring
-// that is roughly chronological; a stale read only costs a redundant one.
-template <int PASS>
-__global__ __launch_bounds__(BLK) void k_near_best(const SwNearQuery q) {
+// that is roughly chronological; a stale read only costs a redundant one.  Q: SwNearQuery or SwZoneQuery
+// (what near_candidate reads, best_date, best_seq).
+template <int PASS, class Q>
+__global__ __launch_bounds__(BLK) void k_near_best(const Q q) {
   const int64_t stride = (int64_t)gridDim.x * BLK;
   for (int64_t r = (int64_t)BID * BLK + threadIdx.x; r < q.ring.n_rows; r += stride) {
     int32_t a;
@@ -2014,6 +2032,106 @@ __global__ __launch_bounds__(BLK) void k_near_filter(const SwNearQuery q, uint32
     n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
     return hit;
   });
+  if (lane_id() == 0) {
+    if (n_cand) atomicAdd(&counters[1], n_cand);
+    if (n_bad) atomicAdd(&counters[2], n_bad);
+  }
+}
+
+// ============================================================================ hot-store zone
+// Locations in a zone straight from the ring (sw_store_zone): location rows that pass the row test and
+// lie inside (q.outside: outside) a polygon of up to SW_ZONE_MAX_VTX vertices.  Candidates, validity
+// and `latest` are the near query's (near_candidate, k_near_best).  A row outside the host's box
+// (pipeline/zone.py: zone_box) is outside the polygon with no polygon work.  The rows inside the box
+// are not decided where they are read: about one ring row in four is a location, so a wave that ran
+// the crossing loop for its own rows would pay every edge at a quarter of its lanes.  They are listed
+// in LDS per chunk instead, and ring_compact's tail runs the loop with one listed row per lane
+// (k_zone_mask does the same for the step's zone rules).  No floating-point atomics.
+struct ZoneList {
+  uint32_t rows[STAGE_CHUNK];
+  uint32_t n[2];                // rows listed in even / odd rounds
+};
+
+// core/geo.py contains, operation for operation (the division form; no contraction into fma: the
+// numpy oracle has none).  vt: the vertices in LDS, (lat, lon) each.  An edge divides only when it
+// crosses in longitude, where its two longitudes differ.
+__device__ __forceinline__ bool zone_inside(const double2* vt, int n_vtx, double lat, double lon) {
+#pragma clang fp contract(off)
+  uint32_t inside = 0;
+  double2 pj = vt[n_vtx - 1];
+  bool sj = pj.y > lon;                       // a vertex's side is asked once and kept for the next edge
+  auto edge = [&](const double2 pi) {
+#pragma clang fp contract(off)
+    const bool si = pi.y > lon;
+    if (si != sj) inside ^= (uint32_t)(lat < (pj.x - pi.x) * (lon - pi.y) / (pj.y - pi.y) + pi.x);
+    pj = pi;
+    sj = si;
+  };
+  // four LDS reads in flight ahead of the four tests: with one read and one test per turn the 1024-vertex
+  // query took 31.7 ms a call against 19.3 ms (profiles/hot_zone/README.md)
+  int i = 0;
+  for (; i + 4 <= n_vtx; i += 4) {
+    const double2 p0 = vt[i], p1 = vt[i + 1], p2 = vt[i + 2], p3 = vt[i + 3];
+    edge(p0);
+    edge(p1);
+    edge(p2);
+    edge(p3);
+  }
+  for (; i < n_vtx; ++i) edge(vt[i]);
+  return inside != 0;
+}
+
+// counters: [0] matches (past cap too), [1] candidates, [2] invalid candidates.  Dynamic LDS: 16 B per vertex.
+__global__ __launch_bounds__(BLK) void k_zone_filter(const SwZoneQuery q, uint32_t* __restrict__ out_rows, int64_t cap,
+                                                     uint32_t* __restrict__ counters) {
+  extern __shared__ double2 zone_vt[];
+  __shared__ ZoneList zl;
+  const int n_vtx = (int)q.n_vtx;
+  for (int i = threadIdx.x; i < n_vtx; i += BLK) zone_vt[i] = make_double2(q.vtx[2 * i], q.vtx[2 * i + 1]);
+  if (threadIdx.x == 0) zl.n[0] = zl.n[1] = 0;          // ring_compact's first barrier stands behind both
+  const bool outside = q.outside != 0;
+  uint32_t n_cand = 0, n_bad = 0;
+  int par = 0;                                          // the round's word of zl.n
+  ring_compact<false>(
+      q.ring.n_rows, out_rows, nullptr, cap, &counters[0],
+      [&](int64_t r, double*) {
+        int32_t a = 0;
+        int64_t d = 0;
+        double lat = 0.0, lon = 0.0;
+        const int cls = near_candidate(q, r, &a, &d, &lat, &lon);
+        bool hit = false, listed = false;
+        if (cls == NEAR_VALID && (!q.latest || (q.best_date[a] == d && q.best_seq[a] == ring_seq(q.ring, r)))) {
+          listed = lat >= q.lat_lo && lat <= q.lat_hi && lon >= q.lon_lo && lon <= q.lon_hi;
+          hit = !listed && outside;
+        }
+        n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
+        n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
+        const ull mask = __ballot(listed);
+        if (mask) {
+          uint32_t base = 0;
+          if (lane_id() == 0) base = atomicAdd(&zl.n[par], (uint32_t)__popcll(mask));
+          base = __shfl(base, 0, 64);
+          if (listed) zl.rows[base + (uint32_t)__popcll(mask & lanemask_lt())] = (uint32_t)r;   // < STAGE_CHUNK: one per row
+        }
+        return hit;
+      },
+      [&](auto& push) {
+        __syncthreads();                                // the chunk's list is whole
+        const uint32_t n = zl.n[par];
+        // the other word was last read a round ago and is next added to a round on, behind the barrier after this
+        if (threadIdx.x == 0) zl.n[par ^ 1] = 0;
+        for (uint32_t i0 = 0; i0 < n; i0 += BLK) {
+          const uint32_t i = i0 + threadIdx.x;
+          uint32_t row = 0;
+          bool hit = false;
+          if (i < n) {
+            row = zl.rows[i];
+            hit = zone_inside(zone_vt, n_vtx, q.v0[row], q.v1[row]) != outside;
+          }
+          push(hit, row, 0.0);
+        }
+        par ^= 1;
+      });
   if (lane_id() == 0) {
     if (n_cand) atomicAdd(&counters[1], n_cand);
     if (n_bad) atomicAdd(&counters[2], n_bad);
@@ -2542,6 +2660,29 @@ int sw_store_near(const SwNearQuery* q, uint32_t* out_rows, double* out_dist, in
   return (int)hipGetLastError();
 }
 
+// Locations in a zone: matches of *q as ring rows into out_rows [cap], unordered; counters (u32[3],
+// zeroed here) as sw_store_near's.  q->latest: best_date / best_seq [n_asg] hold INT64_MIN on entry.
+// The query is refused, before any launch, unless the vertex count is in range, the table is there and
+// the box is finite and ordered.
+int sw_store_zone(const SwZoneQuery* q, uint32_t* out_rows, int64_t cap, uint32_t* counters, hipStream_t s) {
+  const bool poly = q->n_vtx >= 3 && q->n_vtx <= SW_ZONE_MAX_VTX && q->vtx;
+  const bool box = fabs(q->lat_lo) <= 90.0 && fabs(q->lat_hi) <= 90.0 && fabs(q->lon_lo) <= 180.0 &&
+                   fabs(q->lon_hi) <= 180.0 && q->lat_lo <= q->lat_hi && q->lon_lo <= q->lon_hi;
+  const SwRingView& v = q->ring;
+  if (!poly || !box || v.start > v.end || v.n_rows < 1 || v.n_rows > ((int64_t)1 << 32) || v.n_asg < 1 || cap < 1 ||
+      v.head < 0 || v.head >= v.n_rows || (q->latest && (!q->best_date || !q->best_seq)))
+    return (int)hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(counters, 0, 3 * sizeof(uint32_t), s);
+  if (e != hipSuccess) return (int)e;
+  if (q->latest) {
+    k_near_best<0><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
+    k_near_best<1><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
+  }
+  k_zone_filter<<<grid_for((v.n_rows + STAGE_U - 1) / STAGE_U), BLK, (size_t)q->n_vtx * sizeof(double2), s>>>(
+      *q, out_rows, cap, counters);
+  return (int)hipGetLastError();
+}
+
 int sw_state_lookup(const SwMsSlot* ms, int64_t mask, int32_t asg, int32_t n_ids, SwMsSlot* out, uint32_t* n_out,
                     hipStream_t s) {
   hipError_t e = hipMemsetAsync(n_out, 0, sizeof(uint32_t), s);
@@ -2673,6 +2814,7 @@ int sw_abi_sizes(int64_t* out) {
   out[11] = sizeof(SwNearQuery);
   out[12] = sizeof(SwRingView);
   out[13] = sizeof(SwSeriesQuery);
+  out[14] = sizeof(SwZoneQuery);
   return 0;
 }
 

@@ -333,6 +333,25 @@ typedef struct SwNearQuery {
 } SwNearQuery;
 static_assert(sizeof(SwNearQuery) == 176, "SwNearQuery is 22 8-byte words");
 
+// A locations-in-zone query (sw_store_zone; ZONE_QUERY names the words, the doubles written by their
+// bits).  The polygon is planar in (lat, lon), its ring implicitly closed; the box is the host's cover
+// of it (pipeline/zone.py: zone_box), edges included: a point outside the box is outside the polygon.
+typedef struct SwZoneQuery {
+  SwRingView ring;             // ring.n_asg is also the entries of the two tables below
+  const double* v0;            // ring columns: latitude
+  const double* v1;            // longitude
+  const double* vtx;           // [2 * n_vtx] vertices as (lat, lon) pairs
+  int64_t n_vtx;               // 3 .. SW_ZONE_MAX_VTX
+  double lat_lo, lat_hi, lon_lo, lon_hi;
+  int64_t outside;             // 1: a valid candidate matches when it is not inside
+  int64_t latest;              // 1: keep a row only if it is its assignment's newest valid candidate
+  int64_t* best_date;          // [n_asg] latest only: date of that row, then its store sequence
+  int64_t* best_seq;
+} SwZoneQuery;
+static_assert(sizeof(SwZoneQuery) == 176, "SwZoneQuery is 22 8-byte words");
+
+#define SW_ZONE_MAX_VTX 1024
+
 #define SW_N_STATS 24
 
 enum {

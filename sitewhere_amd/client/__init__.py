@@ -347,3 +347,9 @@ class SiteWhereClient:
         ``distance``; ``page`` / ``pageSize``).  Search results of locations, each with ``distance``."""
         return self.get(f"/search/{provider_id}/locations/near", latitude=latitude, longitude=longitude,
                         distance=distance, **crit)
+
+    def locations_in_zone(self, zone_token: str, provider_id: str = "events", **crit):
+        """Locations inside a zone (``startDate`` / ``endDate``; ``outside``: the locations outside it;
+        ``latest``: only each assignment's newest location in the range is looked at; ``page`` /
+        ``pageSize``).  Search results of locations, newest first."""
+        return self.get(f"/search/{provider_id}/locations/zone/{zone_token}", **crit)

@@ -144,6 +144,11 @@ SERIES_QUERY = RING_QUERY + ("name", "v0", "names", "n_names", "bucket_ms", "n_b
 NEAR_QUERY = RING_QUERY + ("v0", "v1", "lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "latest",
                            "best_date", "best_seq")
 NEAR_QUERY_F64 = ("lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi")
+# The 8-byte words of a locations-in-zone query (SwZoneQuery in swengine.h), in order; ZONE_QUERY_F64 are
+# the doubles among them.
+ZONE_QUERY = RING_QUERY + ("v0", "v1", "vtx", "n_vtx", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "outside", "latest",
+                           "best_date", "best_seq")
+ZONE_QUERY_F64 = ("lat_lo", "lat_hi", "lon_lo", "lon_hi")
 
 # Durable-block encoder state (u64 words): the result words follow the max_pages look-back words
 # (SEG_ST_* in swseg.h) -- block bytes (~0 on error), errors, store sequence of the first row.

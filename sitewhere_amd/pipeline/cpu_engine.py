@@ -708,6 +708,22 @@ class CpuInboundEngine(EngineBase):
         info = {"candidates": len(rows), "invalid": n_invalid, "hot_since": self._hot_since(self.cursor)}
         return len(sel), cols, seq[sel[lo:hi]] * self.world + self.rank, dist[lo:hi], info
 
+    def zone_store(self, polygon, asg_idx=None, start=None, end=None, outside=False, latest=False, page_number=1,
+                   page_size=100):
+        """The oracle of the MI355X zone kernel: a numpy filter, then ``zone.zone_select`` over every
+        candidate (no bounding-box prefilter)."""
+        from .zone import check_zone_args, zone_select
+        poly = check_zone_args(polygon, start, end)
+        s = self.store
+        rows, d, seq = self._ring_candidates(EV_LOCATION, asg_idx, start, end)
+        sel, n_invalid = zone_select(s["asg"][rows], d, seq, s["v0"][rows], s["v1"][rows], poly, bool(outside),
+                                     bool(latest))
+        lo, hi = self._window(page_number, page_size, len(sel))
+        page = rows[sel[lo:hi]]
+        cols = {k: v[page] for k, v in s.items()}
+        info = {"candidates": len(rows), "invalid": n_invalid, "hot_since": self._hot_since(self.cursor)}
+        return len(sel), cols, seq[sel[lo:hi]] * self.world + self.rank, info
+
     def intern_table(self) -> dict:
         """name hash -> dense name id (same form as the GPU and native engines)."""
         return dict(self.intern)

@@ -468,6 +468,29 @@ class EngineBase:
         oracle's, and in distance order two rows closer than the band to each other may swap."""
         raise NotImplementedError
 
+    def zone_store(self, polygon, asg_idx=None, start: int | None = None, end: int | None = None,
+                   outside: bool = False, latest: bool = False, page_number: int = 1, page_size: int = 100):
+        """Location rows of this shard's event ring inside (``outside``: outside) a zone.  ``polygon`` is
+        an (N, 2) float64 array of (lat, lon) vertices (``core/geo.polygon_of``), 3 <= N <=
+        ``ZONE_MAX_VTX`` (1024), the ring implicitly closed.  It is planar in (lat, lon), as the
+        reference's JTS test and the zone rules treat it: a zone that crosses the antimeridian is not
+        special-cased.  Candidates and validity are :meth:`near_store`'s: a location row whose assignment
+        is in ``asg_idx`` (None: every assignment) and whose date lies in [start, end]; one whose
+        latitude or longitude is not finite or out of range is invalid -- counted, never returned,
+        whether or not ``outside`` is set.  The predicate is ``core/geo.contains`` operation for
+        operation in fp64 (division form, no fma): every operation is correctly rounded on every engine,
+        so membership is identical everywhere, on a vertex or an edge too -- there is no band.  A valid
+        candidate matches when ``inside != outside``.  ``latest``: of each assignment only the valid
+        candidate with the largest (date, event id) is looked at, and it matches only if it satisfies
+        the containment itself (``latest=True, outside=False``: who is in the zone now).  Order: (date
+        desc, event id desc).
+
+        Returns (total, cols, eids, info): as :meth:`query_store` returns them, and ``info`` =
+        ``{"candidates", "invalid", "hot_since"}`` as in :meth:`near_store`.  ``ValueError``
+        (``pipeline/zone.py: check_zone_args``) for a polygon outside those limits, a vertex that is not
+        finite or out of range, or ``start > end``."""
+        raise NotImplementedError
+
     @staticmethod
     def _window(page_number: int, page_size: int, total: int) -> tuple[int, int]:
         if page_size <= 0:

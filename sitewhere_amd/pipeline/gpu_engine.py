@@ -26,7 +26,7 @@ from .._native import gpu_gil as gpu_lib
 from ..models.columnar import (EVENT_REC, N_STATS, NEAR_QUERY, NEAR_QUERY_F64, OUT_REC, NAME_REF, OUT_REC_SIZE, RING_QUERY,
                                SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK, SC_N_OUT, SC_N_RECS, SC_N_REJ, SC_N_RULE, SC_N_WORK,
                                SC_NAMES, SC_OVERFLOW, SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, SERIES_CELL, SERIES_QUERY,
-                               ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC)
+                               ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC, ZONE_QUERY, ZONE_QUERY_F64)
 from ..ops.engine_abi import SwEngineArgs
 from .config import EngineConfig
 from .bus_io import host_view
@@ -1462,6 +1462,63 @@ class GpuInboundEngine(EngineBase):
         cols, eids, dist = self._order_page(rows[:total].long() & 0xFFFFFFFF, cur, page_number, page_size, dist[:total],
                                             order == "distance")
         return total, cols, eids, dist, info
+
+    def zone_store(self, polygon, asg_idx=None, start=None, end=None, outside=False, latest=False, page_number=1,
+                   page_size=100):
+        """Locations in a zone on the MI355X (``sw_store_zone``, csrc/hip/swgpu.hip): one ``k_zone_filter``
+        pass over the HBM ring stages the polygon in LDS, tests candidates against the host's box
+        (``zone.zone_box``) and runs the fp64 crossing loop only for rows inside it, one listed row per
+        lane; matches are compacted as ring rows.  ``latest`` runs the two ``k_near_best`` passes ahead.
+        The match set is ordered on the device and only the page crosses PCIe.  No floating-point atomics
+        and a total order, so an unchanged ring gives the same answer every time.  Runs on the caller's
+        current stream in buffers of its own, outside the captured step graph; holds the engine lock like
+        :meth:`query_store`."""
+        from .zone import check_zone_args
+        poly = check_zone_args(polygon, start, end)
+        with self._lock:
+            return self._zone_store(poly, asg_idx, start, end, bool(outside), bool(latest), page_number, page_size)
+
+    _zone_rows0 = 1 << 20          # first size of zone_store's match buffer, in rows (4 B each)
+
+    def _zone_store(self, poly, asg_idx, start, end, outside, latest, page_number, page_size):
+        from .zone import zone_box
+        st = self.store
+        info = {"candidates": 0, "invalid": 0, "hot_since": None}
+        cur, view, bits = self._ring_view(asg_idx, start, end)
+        n, nbits = view["n_rows"], view["n_asg"]
+        if n == 0:
+            cols = {k: torch.empty(0, dtype=v.dtype).numpy() for k, v in st.items()}       # host tensors: no launch
+            return 0, self._u64_cols(cols), np.zeros(0, np.int64), info
+        info["hot_since"] = self._hot_since(cur)
+        buf = functools.partial(self._ring_buf, "zone")
+        best = None
+        if latest:
+            best = buf("best", 2 * nbits, torch.int64)
+            best[:2 * nbits].fill_(_I64.min)
+        vtx = buf("vtx", 2 * len(poly), torch.float64)
+        vtx[:2 * len(poly)].copy_(torch.from_numpy(poly.reshape(-1)))
+        lat_lo, lat_hi, lon_lo, lon_hi = zone_box(poly)
+        q = self._query_words(ZONE_QUERY, ZONE_QUERY_F64, dict(
+            view, v0=_ptr(st["v0"]), v1=_ptr(st["v1"]), vtx=_ptr(vtx), n_vtx=len(poly), lat_lo=lat_lo, lat_hi=lat_hi,
+            lon_lo=lon_lo, lon_hi=lon_hi, outside=int(outside), latest=int(latest),
+            best_date=_ptr(best) if latest else 0, best_seq=_ptr(best) + 8 * nbits if latest else 0))
+        counters = buf("counters", 3)
+        # the match buffer starts at _zone_rows0 rows (or what an earlier query grew it to); when that is
+        # short it grows to the match count and the pass is repeated
+        held = self._ring_bufs["zone"].get("rows")
+        cap = min(n, max(self._zone_rows0, 0 if held is None else held.numel()))
+        stream = self._stream()
+        while True:
+            rows = buf("rows", cap)
+            _chk(self.lib.sw_store_zone(q.ctypes.data, _ptr(rows), cap, _ptr(counters), stream), "sw_store_zone")
+            total, info["candidates"], info["invalid"] = (int(x) for x in counters[:3].cpu().numpy().view(np.uint32))
+            if total <= cap:
+                break
+            cap = total
+            if latest:
+                best[:2 * nbits].fill_(_I64.min)
+        cols, eids, _ = self._order_page(rows[:total].long() & 0xFFFFFFFF, cur, page_number, page_size)
+        return total, cols, eids, info
 
     @staticmethod
     def _u64_cols(cols):

@@ -1372,6 +1372,30 @@ class GpuInboundApi:
         return {"hotSince": info["hot_since"], "numResults": int(total), "results": [ev for ev, _ in evs],
                 "distances": [float(dist[i]) for _, i in evs]}
 
+    def locations_in_zone_hot(self, polygon, start_date: int | None = None, end_date: int | None = None,
+                              index: str | None = None, entity_ids: list | None = None, outside: bool = False,
+                              latest: bool = False, page_number: int = 1, page_size: int = 100) -> dict:
+        """Locations inside (``outside``: outside) a zone from the engine's event ring
+        (``EngineBase.zone_store``: on the MI355X the scan and the polygon test run in HBM and only the
+        page crosses PCIe).  ``polygon``: (N, 2) (lat, lon) vertices, as ``core/geo.polygon_of`` gives
+        them.  ``index`` None: tenant-wide, else the locations of ``entity_ids`` under that index as in
+        :meth:`list_hot_events`.  ``latest``: only each assignment's newest location in the range is
+        looked at (with ``outside`` off: who is in the zone now).  Returns ``{"hotSince", "numResults",
+        "results"}``, newest first; ``hotSince`` as in :meth:`locations_near_hot`.  ``ValueError`` for
+        arguments ``zone_store`` refuses."""
+        e = self._e
+        asg = None
+        if index is not None:
+            pos = self._INDEX[index]
+            want = set(entity_ids or [])
+            with e._lock:
+                asg = [ai for ai, a in e._asg_entities.items()
+                       if (a.id, a.device_id, a.customer_id, a.area_id, a.asset_id)[pos] in want]
+        total, cols, eids, info = e.engine.zone_store(polygon, asg, start_date, end_date, outside, latest, page_number,
+                                                      page_size)
+        return {"hotSince": info["hot_since"], "numResults": int(total),
+                "results": [ev for ev, _ in self._hot_events(cols, eids)]}
+
     def measurement_series_hot(self, index: str, entity_ids: list, measurement_ids: list | None, start_date: int,
                                end_date: int, bucket_ms: int) -> dict:
         """Measurement series in time buckets from the engine's event ring

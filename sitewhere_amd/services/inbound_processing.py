@@ -321,6 +321,12 @@ class InboundProcessingApi:
         engine keeps none, so None -- the caller filters event management's list instead."""
         return None
 
+    def locations_in_zone_hot(self, polygon, start_date=None, end_date=None, index=None, entity_ids=None,
+                              outside=False, latest=False, page_number=1, page_size=100):
+        """Locations in a zone from a hot store (``GpuInboundApi.locations_in_zone_hot``): the per-event
+        engine keeps none, so None -- the caller filters event management's list instead."""
+        return None
+
 
 class InboundProcessingMicroservice(MultitenantMicroservice):
     identifier = "inbound-processing"

@@ -173,6 +173,10 @@ class SolrSearchProvider:
         of the reference answers."""
         return {"hotSince": None, "numResults": 0, "results": [], "distances": []}
 
+    def get_locations_in_zone(self, zone_token: str, criteria=None) -> dict:
+        """No geospatial query is sent to Solr: an empty result, as for :meth:`get_locations_near`."""
+        return {"hotSince": None, "numResults": 0, "results": []}
+
 
 class EventStoreSearchProvider:
     """In-process provider: ``field:value`` terms (AND) over the tenant's event store."""
@@ -228,6 +232,41 @@ class EventStoreSearchProvider:
             {"pageNumber": 1, "pageSize": 0, "startDate": start, "endDate": end}).results
         return host_near(locs, latitude, longitude, distance, start, end, latest, order, page, size)
 
+    def get_locations_in_zone(self, zone_token: str, criteria=None) -> dict:
+        """The tenant's locations inside a zone (``Zone.bounds`` as a planar (lat, lon) polygon, the
+        test ``core/geo.contains``).  ``criteria``: a date-range criteria object or a dict (``startDate``,
+        ``endDate``, ``pageNumber``, ``pageSize``, and the additions ``outside``: the locations outside
+        the zone, and ``latest``: only each assignment's newest location in the range is looked at).
+        Served from the inbound engine's event ring when the tenant has one and the ring covers the
+        range, by :meth:`get_locations_near`'s rule, else from event management's list of the range's
+        locations, filtered on the host by the same function (``pipeline/zone.py``); a zone of more
+        than ``ZONE_MAX_VTX`` bounds always takes the host route.  Returns ``{"hotSince", "numResults",
+        "results"}``, newest first.  An unknown zone is not found; ``ValueError`` for a zone of fewer
+        than 3 bounds or ``startDate > endDate``."""
+        from ..core.geo import polygon_of
+        from ..pipeline.zone import ZONE_MAX_VTX, check_zone_args, host_zone
+        c = criteria or {}
+        if not isinstance(c, dict):
+            c = {"startDate": c.start_date, "endDate": c.end_date, "pageNumber": c.page_number, "pageSize": c.page_size}
+        start, end = c.get("startDate"), c.get("endDate")
+        outside, latest = bool(c.get("outside", False)), bool(c.get("latest", False))
+        page, size = int(c.get("pageNumber") or 1), int(c.get("pageSize", 100))
+        token = self._e.tenant.token
+        zone = self._e.ms.api("DeviceManagement", token).get_zone_by_token(zone_token)
+        if zone is None:
+            raise NotFoundException(ErrorCode.Error, f"zone {zone_token}")
+        poly = check_zone_args(polygon_of(zone.bounds or []), start, end, max_vtx=None)
+        if len(poly) <= ZONE_MAX_VTX:
+            hot = self._e.ms.api("InboundProcessing", token).locations_in_zone_hot(
+                poly, start, end, None, None, outside, latest, page, size)
+            if hot is not None and (hot["hotSince"] is None or (start is not None and start >= hot["hotSince"])):
+                return hot
+        asgs = self._e.ms.api("DeviceManagement", token).list_device_assignments({"pageNumber": 1, "pageSize": 0})
+        locs = self._e.ms.api("DeviceEventManagement", token).list_locations_for_index(
+            "Assignment", [a.id for a in asgs.results],
+            {"pageNumber": 1, "pageSize": 0, "startDate": start, "endDate": end}).results
+        return host_zone(locs, poly, start, end, outside, latest, page, size)
+
 
 class SearchProviderManager:
     def __init__(self, providers: dict):
@@ -249,6 +288,13 @@ class SearchProviderManager:
         if p is None:
             raise NotFoundException(ErrorCode.Error, f"search provider {provider_id}")
         return p.get_locations_near(latitude, longitude, distance, criteria)
+
+    def get_locations_in_zone(self, provider_id: str, zone_token: str, criteria=None) -> dict:
+        """Locations in a zone on one provider (see the providers' methods)."""
+        p = self._p.get(provider_id)
+        if p is None:
+            raise NotFoundException(ErrorCode.Error, f"search provider {provider_id}")
+        return p.get_locations_in_zone(zone_token, criteria)
 
 
 class EventSearchTenantEngine(MicroserviceTenantEngine):

@@ -906,6 +906,19 @@ def misc_router(web: WebRest) -> APIRouter:
         return {"numResults": res["numResults"],
                 "results": [dict(out(ev), distance=d) for ev, d in zip(res["results"], res["distances"])]}
 
+    @r.get("/search/{providerId}/locations/zone/{zoneToken}")
+    def locations_in_zone(providerId: str, zoneToken: str, startDate: str | None = None, endDate: str | None = None,
+                          outside: bool = False, latest: bool = False, page: int = 1, pageSize: int = 100,
+                          c: Ctx = TENANT):
+        """Locations inside a zone (``outside``: outside it), newest first; ``latest``: only each
+        assignment's newest location in the range is looked at.  An addition over the reference."""
+        crit = dict(date_paging(page, pageSize, startDate, endDate), outside=outside, latest=latest)
+        try:
+            res = c.svc("EventSearch").get_locations_in_zone(providerId, zoneToken, crit)
+        except ValueError as e:
+            raise SiteWhereSystemException(ErrorCode.IncompleteData, detail=str(e)) from None
+        return {"numResults": res["numResults"], "results": [out(ev) for ev in res["results"]]}
+
     # system -----------------------------------------------------------------------------
     @r.get("/system/version")
     def version(c: Ctx = GLOBAL):
