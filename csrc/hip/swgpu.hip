@@ -1243,6 +1243,7 @@ __global__ void k_persist(SwEngineArgs a, const SwEventRec* __restrict__ R, cons
       aux[seq - c0] = seg_make_aux(r, sr, raw_bytes);
     }
     // ---- state pass 1
+    // Pass-2 work item: ms slot | -2 - assignment for a location | -1 (nothing to merge).
     int64_t slot = -1;
     if (r.etype == SW_EV_MEASUREMENT || r.etype == SW_EV_LOCATION || r.etype == SW_EV_ALERT) {
       // Read the 32 B state once; issue an atomic only where it can change something.  Every
@@ -1252,22 +1253,27 @@ __global__ void k_persist(SwEngineArgs a, const SwEventRec* __restrict__ R, cons
       const ulonglong2 lm = *reinterpret_cast<const ulonglong2*>(&st->last);   // last, missing
       if (lm.x < (ull)now) st->last = (ull)now;
       if (lm.y) st->missing = 0;  // presence detected again
-      const ull d = (ull)r.event_date;
-      if (r.etype == SW_EV_LOCATION) {
-        if (d > st->loc_date) atomicMax((ull*)&st->loc_date, d);
-      } else if (nid >= 0) {
-        // +1 keeps key 0 reserved as empty
-        const ull k = ((((ull)(uint32_t)asg) << 32) | ((ull)(uint32_t)nid << 1) | (r.etype == SW_EV_ALERT ? 1ull : 0ull)) + 1ull;
-        slot = ms_slot(a.ms, a.ms_mask, k);
-        if (slot >= 0) {
-          if (d > a.ms[slot].date) atomicMax((ull*)&a.ms[slot].date, d);
-        } else {
-          atomicAdd((ull*)&a.stats[SW_STAT_STATE_OVERFLOW], 1ull);
+      // A date below zero (a device sent >= 2^63) is persisted but never becomes a last value: no
+      // date merge, no state-map claim (so no overflow either) and no pass-2 work item.  `last` and
+      // `missing` above follow the receive time and are updated all the same.
+      if (r.event_date >= 0) {
+        const ull d = (ull)r.event_date;
+        if (r.etype == SW_EV_LOCATION) {
+          if (d > st->loc_date) atomicMax((ull*)&st->loc_date, d);
+          slot = -2 - (int64_t)asg;
+        } else if (nid >= 0) {
+          // +1 keeps key 0 reserved as empty
+          const ull k = ((((ull)(uint32_t)asg) << 32) | ((ull)(uint32_t)nid << 1) | (r.etype == SW_EV_ALERT ? 1ull : 0ull)) + 1ull;
+          slot = ms_slot(a.ms, a.ms_mask, k);
+          if (slot >= 0) {
+            if (d > a.ms[slot].date) atomicMax((ull*)&a.ms[slot].date, d);
+          } else {
+            atomicAdd((ull*)&a.stats[SW_STAT_STATE_OVERFLOW], 1ull);
+          }
         }
       }
     }
-    // pass-2 work item, coalesced: (ms slot | -2 - assignment for a location | -1, event date)
-    if (r.etype == SW_EV_LOCATION) slot = -2 - (int64_t)asg;
+    // coalesced: (work item, event date)
     reinterpret_cast<longlong2*>(a.ev_slot)[j] = make_longlong2(slot, (int64_t)r.event_date);
   }
   if (a.dd_ff) {

@@ -481,6 +481,7 @@ static inline void state_one(const SwCpuEngine* e, const SwCeTables* t, const Sw
   if ((int64_t)s.last < now_ms) s.last = (uint64_t)now_ms;
   s.missing = 0;
   const int64_t d = r.event_date;
+  if (d < 0) return;   // persisted, but never a last value (docs/PARITY.md, dates below zero)
   if (et == SW_EV_LOCATION) {
     const int64_t cd = (int64_t)s.loc_date;
     if (d > cd) {

@@ -440,6 +440,10 @@ class CpuInboundEngine(EngineBase):
             self.st_last[a] = max(int(self.st_last[a]), now_ms)
             self.st_missing[a] = 0
             d = int(r["event_date"])
+            if d < 0:
+                # a date below zero (a device sent >= 2^63) is persisted but never becomes a last value:
+                # one rule for locations and (name, kind) entries, on every engine (docs/PARITY.md)
+                continue
             eid1 = (base + j) * self.world + self.rank + 1
             if et == EV_LOCATION:
                 if d > int(self.st_loc_date[a]):

@@ -18,6 +18,7 @@ from sitewhere_amd.models.columnar import EV_STATE_CHANGE
 from sitewhere_amd.pipeline.cpu_engine import CpuInboundEngine
 
 from pipeline_scenarios import NOW, setup_fleet, small_cfg, hand_batch, fleet_batch, canon_out
+from state_scenarios import full_state, state_diff
 
 
 def pair(**kw):
@@ -76,15 +77,9 @@ def test_fleet_parity_multi_step_with_state():
     assert np.array_equal(eg, ec)
     for k in ("etype", "dev", "asg", "cust", "area", "asset", "date", "recv"):
         assert sorted(cg[k].tolist()) == sorted(cc[k].tolist()), k
-    # device state for a sample of assignments
-    for a in range(0, 1000, 37):
-        sg, sc = g.device_state(a), c.device_state(a)
-        assert sg["last_interaction"] == sc["last_interaction"]
-        assert sg["measurements"].keys() == sc["measurements"].keys()
-        for name in sc["measurements"]:
-            assert sg["measurements"][name][1] == sc["measurements"][name][1]
-        if sc["last_location"]:
-            assert sg["last_location"][1] == sc["last_location"][1]
+    # the whole device state: every assignment, every (name, kind) entry, dates and winning event ids
+    sg, sc = full_state(g), full_state(c)
+    assert sg == sc, state_diff(sg, sc)
 
 
 def test_presence_parity():

@@ -21,6 +21,7 @@ from sitewhere_amd.pipeline.native_engine import NativeCpuEngine
 from measurement_scenarios import (BOUNDARY_ALERTS, FLEET_RULES, HAND_RULES, alerts_of, boundary_batch, count_hits,
                                    many_rules, rows)
 from pipeline_scenarios import NOW, fleet_batch, setup_fleet, small_cfg
+from state_scenarios import full_state, state_diff
 
 EMPTY = (np.zeros(64, np.uint8), np.zeros(1, np.uint32))
 
@@ -90,10 +91,8 @@ def test_fleet_several_tiles_with_zone_tests():
         assert count_hits(rc.prec, FLEET_RULES) > 100
     assert g.stats_dict() == c.stats_dict()
     same_store(g, c)
-    for a in range(0, 1000, 37):
-        sg, sc = g.device_state(a), c.device_state(a)
-        assert sg["last_interaction"] == sc["last_interaction"]
-        assert sg["alerts"].keys() == sc["alerts"].keys()
+    sg, sc = full_state(g), full_state(c)
+    assert sg == sc, state_diff(sg, sc)
 
 
 def test_measurement_tests_without_zone_tests():

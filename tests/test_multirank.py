@@ -16,6 +16,7 @@ from sitewhere_amd.pipeline.cpu_engine import CpuInboundEngine
 from sitewhere_amd.pipeline.fleet import fingerprints, gen_tokens
 
 from pipeline_scenarios import NOW, fleet_batch, canon_out, SQUARE
+from state_scenarios import full_state, state_diff
 from tests.conftest import gpu_available
 
 W = 3
@@ -127,9 +128,12 @@ def test_gpu_loopback_matches_cpu_oracle():
             assert np.array_equal(gres[r].event_ids(), cres[r].event_ids())
     for r in range(W):
         assert g[r].stats_dict() == c[r].stats_dict()
+        # the owner's whole device state: pass 2 maximises ids of the form (cursor + j) * world + rank
+        sg, sc = full_state(g[r]), full_state(c[r])
+        assert sg == sc, (r, state_diff(sg, sc))
 
 
-SPILL = dict(shuffle_slack=0.1, shuffle_pad=0)     # slabs of ~270 records: every step spills
+SPILL =dict(shuffle_slack=0.1, shuffle_pad=0)     # slabs of ~270 records: every step spills
 
 
 def test_cpu_spill_defers_and_conserves_events():
