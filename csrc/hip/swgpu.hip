@@ -1680,7 +1680,7 @@ __global__ void k_step_end(SwEngineArgs a, const uint32_t* n_rule_alerts) {
 }
 
 // ============================================================================ hot-store queries
-// What the four reads over the HBM event ring share, beside their view of it (SwRingView, swengine.h).
+// What the five reads over the HBM event ring share, beside their view of it (SwRingView, swengine.h).
 
 // Store sequence of ring row r: the ring's oldest row is `head`.
 __device__ __forceinline__ int64_t ring_seq(const SwRingView& v, int64_t r) {
@@ -1971,8 +1971,8 @@ __global__ __launch_bounds__(BLK) void k_series_carry(const SwSeriesCell* __rest
 // if it is that one.  No floating-point atomics.
 enum { NEAR_NO = 0, NEAR_INVALID = 1, NEAR_VALID = 2 };
 
-// The row's class; for a candidate (valid or not) *a, *d, *lat, *lon are its columns.  Q: SwNearQuery or
-// SwZoneQuery (ring, v0, v1).
+// The row's class; for a candidate (valid or not) *a, *d, *lat, *lon are its columns.  Q: SwNearQuery,
+// SwZoneQuery or SwGridQuery (ring, v0, v1).
 template <class Q>
 __device__ __forceinline__ int near_candidate(const Q& q, int64_t r, int32_t* a, int64_t* d, double* lat,
                                               double* lon) {
@@ -1996,8 +1996,8 @@ __device__ __forceinline__ double near_haversine(double p1, double cos_p1, doubl
 
 // PASS 0: best_date[a] = newest date among a's valid candidates; PASS 1: best_seq[a] = largest store
 // sequence among those at that date.  The plain read ahead of the atomic saves most atomics on a ring
-// that is roughly chronological; a stale read only costs a redundant one.  Q: SwNearQuery or SwZoneQuery
-// (what near_candidate reads, best_date, best_seq).
+// that is roughly chronological; a stale read only costs a redundant one.  Q: SwNearQuery, SwZoneQuery
+// or SwGridQuery (what near_candidate reads, best_date, best_seq).
 template <int PASS, class Q>
 __global__ __launch_bounds__(BLK) void k_near_best(const Q q) {
   const int64_t stride = (int64_t)gridDim.x * BLK;
@@ -2141,6 +2141,104 @@ __global__ __launch_bounds__(BLK) void k_zone_filter(const SwZoneQuery q, uint32
   if (lane_id() == 0) {
     if (n_cand) atomicAdd(&counters[1], n_cand);
     if (n_bad) atomicAdd(&counters[2], n_bad);
+  }
+}
+
+// ============================================================================ hot-store grid
+// A location density grid straight from the ring (sw_store_grid): the location rows that pass the row
+// test, counted per cell of a lat/lon box cut into n_rows x n_cols cells, with the newest date of each
+// cell.  Candidates, validity and `latest` are the near query's (near_candidate, k_near_best).  One pass
+// over three columns and a histogram: no row leaves HBM.  A hot cell, or a 1 x 1 grid, puts every
+// increment on one address, so up to the host's limit of cells (at most SW_GRID_LDS_CELLS) a
+// workgroup counts in a table of its own in dynamic LDS (a uint32 count and an int64 date per cell, LDS
+// integer atomics) and merges its non-empty cells into the global table at the end, one atomicAdd and
+// at most one atomicMax each; a larger grid goes straight to the global table
+// (profiles/hot_grid/README.md).  Integer atomics only, so the table is the same in any order.
+
+__global__ __launch_bounds__(BLK) void k_grid_init(SwGridCell* __restrict__ cells, int64_t n_cells) {
+  const int64_t i = (int64_t)BID * BLK + threadIdx.x;   // the launch covers n_cells <= SW_GRID_MAX_CELLS
+  if (i < n_cells) {
+    cells[i].count = 0;
+    cells[i].last_date = INT64_MIN;
+  }
+}
+
+// pipeline/grid.py grid_cell_np, operation for operation (nothing contracted).  Whether (lat, lon), a
+// valid position, lies in the box; *cell = its cell, row-major, below n_rows * n_cols: neither quotient
+// is negative (a crossing box gets here with off in [-360, 0) or >= 0) and both are clamped.
+__device__ __forceinline__ bool grid_cell(const SwGridQuery& q, double lat, double lon, uint32_t* cell) {
+#pragma clang fp contract(off)
+  const bool in_lon = q.crossing ? (lon >= q.lon_lo || lon <= q.lon_hi) : (lon >= q.lon_lo && lon <= q.lon_hi);
+  if (!(lat >= q.lat_lo && lat <= q.lat_hi && in_lon)) return false;
+  int64_t i = (int64_t)((lat - q.lat_lo) / q.d_lat);
+  if (i > q.n_rows - 1) i = q.n_rows - 1;
+  double off = lon - q.lon_lo;
+  if (off < 0) off = off + 360.0;
+  int64_t j = (int64_t)(off / q.d_lon);
+  if (j > q.n_cols - 1) j = q.n_cols - 1;
+  *cell = (uint32_t)(i * q.n_cols + j);
+  return true;
+}
+
+// The newest date of a global cell: the plain read ahead of the atomic is k_near_best's.
+__device__ __forceinline__ void grid_date(SwGridCell* __restrict__ cells, uint32_t cell, int64_t d) {
+  if (cells[cell].last_date < d) atomicMax((long long*)&cells[cell].last_date, (long long)d);
+}
+
+// counters: [0] candidates, [1] invalid candidates, [2] valid looked-at rows outside the box.
+// LDS: 12 B of dynamic LDS per cell, the dates first.
+template <bool LDS>
+__global__ __launch_bounds__(BLK) void k_grid_count(const SwGridQuery q, SwGridCell* __restrict__ cells,
+                                                    uint32_t* __restrict__ counters) {
+  extern __shared__ int64_t grid_tab[];
+  const uint32_t n_cells = (uint32_t)(q.n_rows * q.n_cols);
+  int64_t* const l_date = grid_tab;
+  uint32_t* const l_count = (uint32_t*)(grid_tab + n_cells);
+  if constexpr (LDS) {
+    for (uint32_t c = threadIdx.x; c < n_cells; c += BLK) {
+      l_date[c] = INT64_MIN;
+      l_count[c] = 0;
+    }
+    __syncthreads();
+  }
+  uint32_t n_cand = 0, n_bad = 0, n_out = 0;
+  const int64_t stride = (int64_t)gridDim.x * BLK;
+  // whole waves take every turn (the ballots count them); a row past the ring is no candidate
+  for (int64_t r0 = (int64_t)BID * BLK; r0 < q.ring.n_rows; r0 += stride) {
+    const int64_t r = r0 + threadIdx.x;
+    int32_t a = 0;
+    int64_t d = 0;
+    double lat = 0.0, lon = 0.0;
+    const int cls = near_candidate(q, r, &a, &d, &lat, &lon);
+    const bool looked = cls == NEAR_VALID && (!q.latest || (q.best_date[a] == d && q.best_seq[a] == ring_seq(q.ring, r)));
+    uint32_t cell = 0;
+    const bool in = looked && grid_cell(q, lat, lon, &cell);
+    n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
+    n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
+    n_out += (uint32_t)__popcll(__ballot(looked && !in));
+    if (in) {
+      if constexpr (LDS) {
+        atomicAdd(&l_count[cell], 1u);          // a workgroup's rows: under 2^32
+        atomicMax((long long*)&l_date[cell], (long long)d);
+      } else {
+        atomicAdd((ull*)&cells[cell].count, 1ull);
+        grid_date(cells, cell, d);
+      }
+    }
+  }
+  if constexpr (LDS) {
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < n_cells; c += BLK) {     // every cell of the table, not the first BLK
+      const uint32_t n = l_count[c];
+      if (!n) continue;
+      atomicAdd((ull*)&cells[c].count, (ull)n);
+      grid_date(cells, c, l_date[c]);
+    }
+  }
+  if (lane_id() == 0) {
+    if (n_cand) atomicAdd(&counters[0], n_cand);
+    if (n_bad) atomicAdd(&counters[1], n_bad);
+    if (n_out) atomicAdd(&counters[2], n_out);
   }
 }
 
@@ -2689,6 +2787,46 @@ int sw_store_zone(const SwZoneQuery* q, uint32_t* out_rows, int64_t cap, uint32_
   return (int)hipGetLastError();
 }
 
+// The cell count up to which sw_store_grid counts in LDS tables: SW_GRID_LDS_CELLS unless lowered here
+// (0: every grid goes straight to the global table), which profiles/hot_grid measures against.
+// cells < 0: no change.  Returns the limit in force.
+static int64_t grid_lds_cells = SW_GRID_LDS_CELLS;
+int64_t sw_grid_lds_cells(int64_t cells) {
+  if (cells >= 0) grid_lds_cells = cells < SW_GRID_LDS_CELLS ? cells : SW_GRID_LDS_CELLS;
+  return grid_lds_cells;
+}
+
+// Location density grid: cells [q->n_rows * q->n_cols], row-major, zeroed here (an empty cell's date is
+// left at INT64_MIN); counters (u32[3], zeroed here): candidates, invalid candidates, valid looked-at
+// rows outside the box.  q->latest: best_date / best_seq [n_asg] hold INT64_MIN on entry.  The query is
+// refused, before any launch, unless the box is finite, in range and ordered as `crossing` says, the
+// grid within SW_GRID_MAX_CELLS and the steps positive: what keeps a cell inside the table.
+int sw_store_grid(const SwGridQuery* q, SwGridCell* cells, uint32_t* counters, hipStream_t s) {
+  const bool box = q->lat_lo >= -90.0 && q->lat_lo < q->lat_hi && q->lat_hi <= 90.0 && fabs(q->lon_lo) <= 180.0 &&
+                   fabs(q->lon_hi) <= 180.0 && q->lon_lo != q->lon_hi && (q->crossing != 0) == (q->lon_lo > q->lon_hi);
+  const bool grid = q->n_rows >= 1 && q->n_cols >= 1 && q->n_rows <= SW_GRID_MAX_CELLS &&
+                    q->n_cols <= SW_GRID_MAX_CELLS && q->n_rows * q->n_cols <= SW_GRID_MAX_CELLS && q->d_lat > 0.0 &&
+                    q->d_lon > 0.0 && q->d_lat <= 180.0 && q->d_lon <= 360.0;
+  const SwRingView& v = q->ring;
+  if (!box || !grid || !cells || v.start > v.end || v.n_rows < 1 || v.n_rows > ((int64_t)1 << 32) || v.n_asg < 1 ||
+      v.head < 0 || v.head >= v.n_rows || (q->latest && (!q->best_date || !q->best_seq)))
+    return (int)hipErrorInvalidValue;
+  const int64_t n_cells = q->n_rows * q->n_cols;
+  hipError_t e = hipMemsetAsync(counters, 0, 3 * sizeof(uint32_t), s);
+  if (e != hipSuccess) return (int)e;
+  k_grid_init<<<(unsigned)((n_cells + BLK - 1) / BLK), BLK, 0, s>>>(cells, n_cells);
+  if (q->latest) {
+    k_near_best<0><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
+    k_near_best<1><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
+  }
+  const int g = grid_for((v.n_rows + STAGE_U - 1) / STAGE_U);
+  if (n_cells <= grid_lds_cells)
+    k_grid_count<true><<<g, BLK, (size_t)n_cells * 12, s>>>(*q, cells, counters);
+  else
+    k_grid_count<false><<<g, BLK, 0, s>>>(*q, cells, counters);
+  return (int)hipGetLastError();
+}
+
 int sw_state_lookup(const SwMsSlot* ms, int64_t mask, int32_t asg, int32_t n_ids, SwMsSlot* out, uint32_t* n_out,
                     hipStream_t s) {
   hipError_t e = hipMemsetAsync(n_out, 0, sizeof(uint32_t), s);
@@ -2821,6 +2959,7 @@ int sw_abi_sizes(int64_t* out) {
   out[12] = sizeof(SwRingView);
   out[13] = sizeof(SwSeriesQuery);
   out[14] = sizeof(SwZoneQuery);
+  out[15] = sizeof(SwGridQuery);
   return 0;
 }
 

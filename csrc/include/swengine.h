@@ -352,6 +352,37 @@ static_assert(sizeof(SwZoneQuery) == 176, "SwZoneQuery is 22 8-byte words");
 
 #define SW_ZONE_MAX_VTX 1024
 
+// One cell of a location density grid (sw_store_grid; GRID_CELL in sitewhere_amd/models/columnar.py
+// mirrors it).  The device leaves INT64_MIN in the date of an empty cell; the engine zeroes it.
+typedef struct SwGridCell {
+  int64_t count;
+  int64_t last_date;           // newest event date among the cell's rows
+} SwGridCell;
+static_assert(sizeof(SwGridCell) == 16, "SwGridCell is two 8-byte words");
+
+// A location density-grid query (sw_store_grid; GRID_QUERY names the words, the doubles written by
+// their bits).  The box is closed on all sides; crossing: lon_lo > lon_hi, it crosses the antimeridian.
+// d_lat / d_lon are the host's cell steps (pipeline/grid.py: grid_steps): the cell formula divides by
+// them as they stand, so every engine puts a row in the same cell.
+typedef struct SwGridQuery {
+  SwRingView ring;             // ring.n_asg is also the entries of the two tables below
+  const double* v0;            // ring columns: latitude
+  const double* v1;            // longitude
+  double lat_lo, lat_hi, lon_lo, lon_hi;
+  double d_lat, d_lon;         // a cell's height and width in degrees
+  int64_t n_rows, n_cols;      // the grid; row 0 is the south edge, column 0 the lon_lo one
+  int64_t crossing;
+  int64_t latest;              // 1: count a row only if it is its assignment's newest valid candidate
+  int64_t* best_date;          // [n_asg] latest only: date of that row, then its store sequence
+  int64_t* best_seq;
+} SwGridQuery;
+static_assert(sizeof(SwGridQuery) == 192, "SwGridQuery is 24 8-byte words");
+
+#define SW_GRID_MAX_CELLS 65536
+// Up to this many cells a workgroup of k_grid_count counts in a table of its own in LDS (12 B a cell)
+// and merges it into the global one at the end; above, every row goes to the global table.
+#define SW_GRID_LDS_CELLS 4096
+
 #define SW_N_STATS 24
 
 enum {

@@ -353,3 +353,12 @@ class SiteWhereClient:
         ``latest``: only each assignment's newest location in the range is looked at; ``page`` /
         ``pageSize``).  Search results of locations, newest first."""
         return self.get(f"/search/{provider_id}/locations/zone/{zone_token}", **crit)
+
+    def locations_grid(self, lat_min: float, lat_max: float, lon_min: float, lon_max: float, rows: int, cols: int,
+                       provider_id: str = "events", **crit):
+        """A density grid of locations over a lat/lon box (``startDate`` / ``endDate``; ``latest``: only
+        each assignment's newest location in the range is looked at; ``lon_min > lon_max``: the box
+        crosses the antimeridian).  The non-empty cells of ``rows`` x ``cols`` as ``{"row", "col",
+        "count", "lastDate"}``, with ``numResults``, ``outside``, ``invalid`` and the cell steps."""
+        return self.get(f"/search/{provider_id}/locations/grid", latMin=lat_min, latMax=lat_max, lonMin=lon_min,
+                        lonMax=lon_max, rows=rows, cols=cols, **crit)

@@ -149,6 +149,17 @@ NEAR_QUERY_F64 = ("lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_h
 ZONE_QUERY = RING_QUERY + ("v0", "v1", "vtx", "n_vtx", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "outside", "latest",
                            "best_date", "best_seq")
 ZONE_QUERY_F64 = ("lat_lo", "lat_hi", "lon_lo", "lon_hi")
+# One cell of a location density grid (SwGridCell in swengine.h): the locations in it and the newest of
+# their dates; an empty cell is all zero bytes.
+GRID_CELL = np.dtype([("count", "<i8"), ("last_date", "<i8")])
+assert GRID_CELL.itemsize == 16
+# The 8-byte words of a density-grid query (SwGridQuery in swengine.h), in order; GRID_QUERY_F64 are the
+# doubles among them.  GRID_WORDS are the query's own: its n_rows (the grid's rows) shares its name with the
+# ring view's (the ring's rows), so the two parts are filled in separately.
+GRID_WORDS = ("v0", "v1", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "d_lat", "d_lon", "n_rows", "n_cols", "crossing",
+              "latest", "best_date", "best_seq")
+GRID_QUERY = RING_QUERY + GRID_WORDS
+GRID_QUERY_F64 = ("lat_lo", "lat_hi", "lon_lo", "lon_hi", "d_lat", "d_lon")
 
 # Durable-block encoder state (u64 words): the result words follow the max_pages look-back words
 # (SEG_ST_* in swseg.h) -- block bytes (~0 on error), errors, store sequence of the first row.

@@ -728,6 +728,19 @@ class CpuInboundEngine(EngineBase):
         info = {"candidates": len(rows), "invalid": n_invalid, "hot_since": self._hot_since(self.cursor)}
         return len(sel), cols, seq[sel[lo:hi]] * self.world + self.rank, info
 
+    def grid_store(self, lat_lo, lat_hi, lon_lo, lon_hi, n_rows, n_cols, asg_idx=None, start=None, end=None,
+                   latest=False):
+        """The oracle of the MI355X grid kernel: a numpy filter, then ``grid.grid_select`` over every
+        candidate."""
+        from .grid import check_grid_args, grid_select
+        box, n_rows, n_cols = check_grid_args(lat_lo, lat_hi, lon_lo, lon_hi, n_rows, n_cols, start, end)
+        s = self.store
+        rows, d, seq = self._ring_candidates(EV_LOCATION, asg_idx, start, end)
+        cells, n_invalid, n_outside = grid_select(s["asg"][rows], d, seq, s["v0"][rows], s["v1"][rows], box, n_rows,
+                                                  n_cols, bool(latest))
+        return cells, {"candidates": len(rows), "invalid": n_invalid, "outside": n_outside,
+                       "hot_since": self._hot_since(self.cursor)}
+
     def intern_table(self) -> dict:
         """name hash -> dense name id (same form as the GPU and native engines)."""
         return dict(self.intern)

@@ -491,6 +491,48 @@ class EngineBase:
         finite or out of range, or ``start > end``."""
         raise NotImplementedError
 
+    def grid_store(self, lat_lo: float, lat_hi: float, lon_lo: float, lon_hi: float, n_rows: int, n_cols: int,
+                   asg_idx=None, start: int | None = None, end: int | None = None, latest: bool = False):
+        """A density grid of this shard's location rows: the box [lat_lo, lat_hi] x [lon_lo, lon_hi], closed
+        on all sides, cut into ``n_rows`` x ``n_cols`` cells, each with the number of locations in it and
+        the newest of their dates.  ``-90 <= lat_lo < lat_hi <= 90``; ``lon_lo`` and ``lon_hi`` lie in
+        [-180, 180] and differ; ``lon_lo > lon_hi`` means the box crosses the antimeridian, as
+        ``near.near_box`` may, and its width is then ``lon_hi - lon_lo + 360.0``; ``n_rows, n_cols >= 1``
+        and ``n_rows * n_cols <= GRID_MAX_CELLS`` (65536, the series query's limit).
+
+        Candidates and validity are :meth:`near_store`'s: a location row whose assignment is in
+        ``asg_idx`` (None: every assignment) and whose date lies in [start, end] (None: that side open);
+        one whose latitude or longitude is not finite or out of range is invalid -- counted, in no cell.
+        ``latest``: of each assignment only the valid candidate with the largest (date, event id) is
+        looked at, as in :meth:`near_store` and :meth:`zone_store`; a cell's count is then the number of
+        assignments whose newest position in the range lies in it.
+
+        The cell of a valid looked-at row is one formula on every engine (``pipeline/grid.py:
+        grid_cell_np``), every operation a single correctly rounded fp64 one, nothing contracted, the two
+        steps computed once on the host::
+
+            d_lat = (lat_hi - lat_lo) / n_rows            d_lon = width / n_cols
+            inside:  lat_lo <= lat <= lat_hi  and  (lon_lo <= lon <= lon_hi,  or when crossing:  lon >= lon_lo or lon <= lon_hi)
+            i = min(int((lat - lat_lo) / d_lat), n_rows - 1)          # row 0 is the south edge
+            off = lon - lon_lo;  if off < 0: off = off + 360.0        # only a crossing box gets here with off < 0
+            j = min(int(off / d_lon), n_cols - 1)
+
+        ``int`` truncates a quotient that is never negative; the ``min`` puts the closed north and east
+        edges, and any quotient that rounds up to the cell count, into the last row or column.  Longitude
+        -180 and 180 are the same meridian and are not special-cased: a box from -180 to 180 has them in
+        its first and its last column, a crossing box in one cell (``pipeline/grid.py``).  A valid looked-at row outside the box is counted in ``info["outside"]``.
+
+        Returns (cells, info).  ``cells``: a ``GRID_CELL`` array of shape (n_rows, n_cols) -- ``count``
+        and ``last_date``, the newest event date among the cell's rows; an empty cell is all zero.
+        ``info`` = ``{"candidates", "invalid", "outside", "hot_since"}``, ``hot_since`` as in
+        :meth:`aggregate_store`.  Conservation: without ``latest``, ``cells["count"].sum() + outside + invalid
+        == candidates``; with it, ``cells["count"].sum() + outside`` is the number of assignments that
+        have a valid candidate.  There is no band: counts and dates are integers and the cell formula is
+        exact, so every engine answers with the same bytes, on every call.  ``ValueError``
+        (``pipeline/grid.py: check_grid_args``) for a box or cell counts outside those limits, a bound
+        that is not finite, or ``start > end``."""
+        raise NotImplementedError
+
     @staticmethod
     def _window(page_number: int, page_size: int, total: int) -> tuple[int, int]:
         if page_size <= 0:

@@ -23,9 +23,9 @@ import numpy as np
 import torch
 
 from .._native import gpu_gil as gpu_lib
-from ..models.columnar import (EVENT_REC, N_STATS, NEAR_QUERY, NEAR_QUERY_F64, OUT_REC, NAME_REF, OUT_REC_SIZE, RING_QUERY,
-                               SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK, SC_N_OUT, SC_N_RECS, SC_N_REJ, SC_N_RULE, SC_N_WORK,
-                               SC_NAMES, SC_OVERFLOW, SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, SERIES_CELL, SERIES_QUERY,
+from ..models.columnar import (EVENT_REC, GRID_CELL, GRID_QUERY_F64, GRID_WORDS, N_STATS, NEAR_QUERY, NEAR_QUERY_F64,
+                               OUT_REC, NAME_REF, OUT_REC_SIZE, RING_QUERY, SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK, SC_N_OUT,
+                               SC_N_RECS, SC_N_REJ, SC_N_RULE, SC_N_WORK, SC_NAMES, SC_OVERFLOW, SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, SERIES_CELL, SERIES_QUERY,
                                ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC, ZONE_QUERY, ZONE_QUERY_F64)
 from ..ops.engine_abi import SwEngineArgs
 from .config import EngineConfig
@@ -1519,6 +1519,48 @@ class GpuInboundEngine(EngineBase):
                 best[:2 * nbits].fill_(_I64.min)
         cols, eids, _ = self._order_page(rows[:total].long() & 0xFFFFFFFF, cur, page_number, page_size)
         return total, cols, eids, info
+
+    def grid_store(self, lat_lo, lat_hi, lon_lo, lon_hi, n_rows, n_cols, asg_idx=None, start=None, end=None,
+                   latest=False):
+        """A location density grid on the MI355X (``sw_store_grid``, csrc/hip/swgpu.hip): one
+        ``k_grid_count`` pass over the HBM ring classifies each row as the near query does and counts the
+        valid ones per cell, with the cell's newest date: in a table per workgroup in LDS, merged into the
+        global one at the end, while the grid has at most ``SW_GRID_LDS_CELLS`` cells, else straight in
+        the global table.  ``latest`` runs the two ``k_near_best`` passes ahead.  Only the cell table (16 B
+        a cell) and three counters cross PCIe.  Integer atomics only, so an unchanged ring gives the same
+        bytes every time.  Runs on the caller's current stream in buffers of its own, outside the captured
+        step graph; holds the engine lock like :meth:`query_store`."""
+        from .grid import check_grid_args
+        box, n_rows, n_cols = check_grid_args(lat_lo, lat_hi, lon_lo, lon_hi, n_rows, n_cols, start, end)
+        with self._lock:
+            return self._grid_store(box, n_rows, n_cols, asg_idx, start, end, bool(latest))
+
+    def _grid_store(self, box, n_rows, n_cols, asg_idx, start, end, latest):
+        from .grid import grid_steps
+        st = self.store
+        info = {"candidates": 0, "invalid": 0, "outside": 0, "hot_since": None}
+        cur, view, bits = self._ring_view(asg_idx, start, end)
+        n, nbits = view["n_rows"], view["n_asg"]
+        if n == 0:
+            return np.zeros((n_rows, n_cols), GRID_CELL), info                   # no launch
+        info["hot_since"] = self._hot_since(cur)
+        buf = functools.partial(self._ring_buf, "grid")
+        best = None
+        if latest:
+            best = buf("best", 2 * nbits, torch.int64)
+            best[:2 * nbits].fill_(_I64.min)
+        d_lat, d_lon, crossing = grid_steps(box, n_rows, n_cols)
+        q = np.concatenate([self._query_words(RING_QUERY, (), view), self._query_words(GRID_WORDS, GRID_QUERY_F64, dict(
+            v0=_ptr(st["v0"]), v1=_ptr(st["v1"]), lat_lo=box[0], lat_hi=box[1], lon_lo=box[2], lon_hi=box[3], d_lat=d_lat,
+            d_lon=d_lon, n_rows=n_rows, n_cols=n_cols, crossing=int(crossing), latest=int(latest),
+            best_date=_ptr(best) if latest else 0, best_seq=_ptr(best) + 8 * nbits if latest else 0))])
+        counters = buf("counters", 3)
+        table = buf("cells", 2 * n_rows * n_cols, torch.int64)
+        _chk(self.lib.sw_store_grid(q.ctypes.data, _ptr(table), _ptr(counters), self._stream()), "sw_store_grid")
+        cells = table[:2 * n_rows * n_cols].cpu().numpy().view(GRID_CELL).reshape(n_rows, n_cols)
+        info["candidates"], info["invalid"], info["outside"] = (int(x) for x in counters[:3].cpu().numpy().view(np.uint32))
+        cells["last_date"][cells["count"] == 0] = 0                              # the device leaves INT64_MIN there
+        return cells, info
 
     @staticmethod
     def _u64_cols(cols):

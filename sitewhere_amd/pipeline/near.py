@@ -89,12 +89,10 @@ def in_box(box, lat, lon) -> np.ndarray:
     return (lat >= lat_lo) & (lat <= lat_hi) & in_lon
 
 
-def near_select(groups, dates, ids, lats, lons, lat: float, lon: float, radius_m: float, latest: bool, order: str):
-    """The row test over candidate rows (parallel arrays; ``groups``: the row's assignment, any
-    integer key).  Invalid positions are dropped and counted.  ``latest``: of each group only the valid
-    row with the largest (date, id) stays, and it matches only if it lies inside the radius itself.
-    Returns (indices of the matches in result order, their distances, invalid rows)."""
-    groups, dates, ids = np.asarray(groups, np.int64), np.asarray(dates, np.int64), np.asarray(ids, np.int64)
+def looked_at(groups, dates, ids, lats, lons, latest: bool):
+    """The rows a location query looks at, of candidate rows as int64 arrays (``groups``: the row's
+    assignment): those with a valid position, and with ``latest`` of each group only the one with the
+    largest (date, id).  Returns (their indices, invalid rows).  The near, zone and grid queries share it."""
     ok = valid_position(lats, lons)
     idx = np.flatnonzero(ok)
     n_invalid = int(len(ok) - len(idx))
@@ -102,6 +100,16 @@ def near_select(groups, dates, ids, lats, lons, lat: float, lon: float, radius_m
         o = np.lexsort((ids[idx], dates[idx], groups[idx]))
         g = groups[idx][o]
         idx = idx[o[np.r_[g[1:] != g[:-1], True]]]
+    return idx, n_invalid
+
+
+def near_select(groups, dates, ids, lats, lons, lat: float, lon: float, radius_m: float, latest: bool, order: str):
+    """The row test over candidate rows (parallel arrays; ``groups``: the row's assignment, any
+    integer key).  Invalid positions are dropped and counted.  ``latest``: of each group only the valid
+    row with the largest (date, id) stays, and it matches only if it lies inside the radius itself.
+    Returns (indices of the matches in result order, their distances, invalid rows)."""
+    groups, dates, ids = np.asarray(groups, np.int64), np.asarray(dates, np.int64), np.asarray(ids, np.int64)
+    idx, n_invalid = looked_at(groups, dates, ids, lats, lons, latest)
     dist = haversine_np(lat, lon, np.asarray(lats, np.float64)[idx], np.asarray(lons, np.float64)[idx])
     with np.errstate(invalid="ignore"):
         m = dist <= radius_m

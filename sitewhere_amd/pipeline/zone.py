@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .near import valid_position
+from .near import looked_at
 
 ZONE_MAX_VTX = 1024                  # SW_ZONE_MAX_VTX: the kernel's vertex table is 16 B a vertex in 16 KiB of LDS
 ZONE_LAT_PAD = 1e-9                  # degrees; see zone_box
@@ -83,13 +83,7 @@ def zone_select(groups, dates, ids, lats, lons, polygon, outside: bool, latest: 
     if it satisfies the containment itself.  A valid row matches when ``inside != outside``.  Returns
     (indices of the matches in (date desc, id desc) order, invalid rows)."""
     groups, dates, ids = np.asarray(groups, np.int64), np.asarray(dates, np.int64), np.asarray(ids, np.int64)
-    ok = valid_position(lats, lons)
-    idx = np.flatnonzero(ok)
-    n_invalid = int(len(ok) - len(idx))
-    if latest and len(idx):
-        o = np.lexsort((ids[idx], dates[idx], groups[idx]))
-        g = groups[idx][o]
-        idx = idx[o[np.r_[g[1:] != g[:-1], True]]]
+    idx, n_invalid = looked_at(groups, dates, ids, lats, lons, latest)
     inside = contains_np(polygon, np.asarray(lats, np.float64)[idx], np.asarray(lons, np.float64)[idx])
     idx = idx[inside != bool(outside)]
     return idx[np.lexsort((-ids[idx], -dates[idx]))], n_invalid

@@ -1396,6 +1396,31 @@ class GpuInboundApi:
         return {"hotSince": info["hot_since"], "numResults": int(total),
                 "results": [ev for ev, _ in self._hot_events(cols, eids)]}
 
+    def locations_grid_hot(self, box, n_rows: int, n_cols: int, start_date: int | None = None,
+                           end_date: int | None = None, index: str | None = None, entity_ids: list | None = None,
+                           latest: bool = False) -> dict:
+        """A location density grid from the engine's event ring (``EngineBase.grid_store``: on the MI355X
+        the scan and the histogram run in HBM and only the cells cross PCIe).  ``box``: (lat_lo, lat_hi,
+        lon_lo, lon_hi), closed; ``lon_lo > lon_hi``: it crosses the antimeridian.  ``index`` None:
+        tenant-wide, else the locations of ``entity_ids`` under that index as in :meth:`list_hot_events`.
+        ``latest``: only each assignment's newest location in the range is looked at (where the fleet is
+        now).  Returns ``{"hotSince", "numResults", "outside", "invalid", "rows", "cols", "latStep",
+        "lonStep", "cells"}`` (``pipeline/grid.py: grid_response``): the non-empty cells in row-major order;
+        ``hotSince`` as in :meth:`locations_near_hot`.  ``ValueError`` for arguments ``grid_store``
+        refuses."""
+        from ..pipeline.grid import check_grid_args, grid_response
+        e = self._e
+        box, n_rows, n_cols = check_grid_args(*box, n_rows, n_cols, start_date, end_date)
+        asg = None
+        if index is not None:
+            pos = self._INDEX[index]
+            want = set(entity_ids or [])
+            with e._lock:
+                asg = [ai for ai, a in e._asg_entities.items()
+                       if (a.id, a.device_id, a.customer_id, a.area_id, a.asset_id)[pos] in want]
+        cells, info = e.engine.grid_store(*box, n_rows, n_cols, asg, start_date, end_date, latest)
+        return grid_response(cells, info, box, info["hot_since"])
+
     def measurement_series_hot(self, index: str, entity_ids: list, measurement_ids: list | None, start_date: int,
                                end_date: int, bucket_ms: int) -> dict:
         """Measurement series in time buckets from the engine's event ring

@@ -327,6 +327,12 @@ class InboundProcessingApi:
         engine keeps none, so None -- the caller filters event management's list instead."""
         return None
 
+    def locations_grid_hot(self, box, n_rows, n_cols, start_date=None, end_date=None, index=None, entity_ids=None,
+                           latest=False):
+        """A location density grid from a hot store (``GpuInboundApi.locations_grid_hot``): the per-event
+        engine keeps none, so None -- the caller counts event management's list instead."""
+        return None
+
 
 class InboundProcessingMicroservice(MultitenantMicroservice):
     identifier = "inbound-processing"

@@ -177,6 +177,16 @@ class SolrSearchProvider:
         """No geospatial query is sent to Solr: an empty result, as for :meth:`get_locations_near`."""
         return {"hotSince": None, "numResults": 0, "results": []}
 
+    def get_locations_grid(self, criteria=None) -> dict:
+        """No geospatial query is sent to Solr: an empty grid, as for :meth:`get_locations_near`."""
+        from ..pipeline.grid import check_grid_args, grid_steps
+        c = criteria or {}
+        box, rows, cols = check_grid_args(c.get("latMin"), c.get("latMax"), c.get("lonMin"), c.get("lonMax"),
+                                          c.get("rows"), c.get("cols"), c.get("startDate"), c.get("endDate"))
+        d_lat, d_lon, _ = grid_steps(box, rows, cols)
+        return {"hotSince": None, "numResults": 0, "outside": 0, "invalid": 0, "rows": rows, "cols": cols,
+                "latStep": d_lat, "lonStep": d_lon, "cells": []}
+
 
 class EventStoreSearchProvider:
     """In-process provider: ``field:value`` terms (AND) over the tenant's event store."""
@@ -267,6 +277,32 @@ class EventStoreSearchProvider:
             {"pageNumber": 1, "pageSize": 0, "startDate": start, "endDate": end}).results
         return host_zone(locs, poly, start, end, outside, latest, page, size)
 
+    def get_locations_grid(self, criteria=None) -> dict:
+        """A density grid of the tenant's locations over a lat/lon box (``EngineBase.grid_store`` has the
+        contract).  ``criteria``: a dict of ``latMin``, ``latMax``, ``lonMin``, ``lonMax`` (``lonMin >
+        lonMax``: the box crosses the antimeridian), ``rows``, ``cols``, and optionally ``startDate``,
+        ``endDate`` and ``latest`` (only each assignment's newest location in the range is looked at).
+        Served from the inbound engine's event ring when the tenant has one and the ring covers the range,
+        by :meth:`get_locations_near`'s rule, else from event management's list of the range's locations,
+        counted on the host by the same function (``pipeline/grid.py``).  Returns ``{"hotSince",
+        "numResults", "outside", "invalid", "rows", "cols", "latStep", "lonStep", "cells"}`` on both
+        routes, ``cells`` the non-empty ones as ``{"row", "col", "count", "lastDate"}`` in row-major
+        order; ``ValueError`` for a box or cell counts out of range or ``startDate > endDate``."""
+        from ..pipeline.grid import check_grid_args, host_grid
+        c = criteria or {}
+        start, end, latest = c.get("startDate"), c.get("endDate"), bool(c.get("latest", False))
+        box, rows, cols = check_grid_args(c.get("latMin"), c.get("latMax"), c.get("lonMin"), c.get("lonMax"),
+                                          c.get("rows"), c.get("cols"), start, end)
+        token = self._e.tenant.token
+        hot = self._e.ms.api("InboundProcessing", token).locations_grid_hot(box, rows, cols, start, end, None, None, latest)
+        if hot is not None and (hot["hotSince"] is None or (start is not None and start >= hot["hotSince"])):
+            return hot
+        asgs = self._e.ms.api("DeviceManagement", token).list_device_assignments({"pageNumber": 1, "pageSize": 0})
+        locs = self._e.ms.api("DeviceEventManagement", token).list_locations_for_index(
+            "Assignment", [a.id for a in asgs.results],
+            {"pageNumber": 1, "pageSize": 0, "startDate": start, "endDate": end}).results
+        return host_grid(locs, *box, rows, cols, start, end, latest)
+
 
 class SearchProviderManager:
     def __init__(self, providers: dict):
@@ -295,6 +331,13 @@ class SearchProviderManager:
         if p is None:
             raise NotFoundException(ErrorCode.Error, f"search provider {provider_id}")
         return p.get_locations_in_zone(zone_token, criteria)
+
+    def get_locations_grid(self, provider_id: str, criteria=None) -> dict:
+        """A location density grid on one provider (see the providers' methods)."""
+        p = self._p.get(provider_id)
+        if p is None:
+            raise NotFoundException(ErrorCode.Error, f"search provider {provider_id}")
+        return p.get_locations_grid(criteria)
 
 
 class EventSearchTenantEngine(MicroserviceTenantEngine):

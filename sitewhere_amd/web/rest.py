@@ -919,6 +919,21 @@ def misc_router(web: WebRest) -> APIRouter:
             raise SiteWhereSystemException(ErrorCode.IncompleteData, detail=str(e)) from None
         return {"numResults": res["numResults"], "results": [out(ev) for ev in res["results"]]}
 
+    @r.get("/search/{providerId}/locations/grid")
+    def locations_grid(providerId: str, latMin: float, latMax: float, lonMin: float, lonMax: float, rows: int, cols: int,
+                       startDate: str | None = None, endDate: str | None = None, latest: bool = False, c: Ctx = TENANT):
+        """A density grid (heat map) of locations over a lat/lon box: the non-empty cells of ``rows`` x
+        ``cols``, each with its count and newest date; ``lonMin > lonMax``: the box crosses the
+        antimeridian; ``latest``: only each assignment's newest location in the range is looked at.  An
+        addition over the reference."""
+        crit = dict(date_paging(1, 0, startDate, endDate), latMin=latMin, latMax=latMax, lonMin=lonMin, lonMax=lonMax,
+                    rows=rows, cols=cols, latest=latest)
+        try:
+            res = c.svc("EventSearch").get_locations_grid(providerId, crit)
+        except ValueError as e:
+            raise SiteWhereSystemException(ErrorCode.IncompleteData, detail=str(e)) from None
+        return res
+
     # system -----------------------------------------------------------------------------
     @r.get("/system/version")
     def version(c: Ctx = GLOBAL):
