@@ -1680,7 +1680,7 @@ __global__ void k_step_end(SwEngineArgs a, const uint32_t* n_rule_alerts) {
 }
 
 // ============================================================================ hot-store queries
-// What the five reads over the HBM event ring share, beside their view of it (SwRingView, swengine.h).
+// What the six reads over the HBM event ring share, beside their view of it (SwRingView, swengine.h).
 
 // Store sequence of ring row r: the ring's oldest row is `head`.
 __device__ __forceinline__ int64_t ring_seq(const SwRingView& v, int64_t r) {
@@ -2240,6 +2240,206 @@ __global__ __launch_bounds__(BLK) void k_grid_count(const SwGridQuery q, SwGridC
     if (n_bad) atomicAdd(&counters[1], n_bad);
     if (n_out) atomicAdd(&counters[2], n_out);
   }
+}
+
+// ============================================================================ hot-store ranking
+// Groups of the ring's rows ranked by a statistic (sw_store_rank): the candidates of one event type are
+// grouped by the context they were persisted with (the asg / cust / area / asset column), each group
+// folded into count, min, max and last of v0 and its newest (date, store sequence), and the non-empty
+// groups leave as SwRankCells beside an int64 sort key; the engine orders them and fetches the first k.
+// Values are compared as rank keys (rank_key below), so the whole fold is integer atomics and the table
+// is the same in any order.  Two shapes of key make the fold hard: a hot key puts every update on one
+// address, and assignment keys arrive in runs (a step's rows persist clustered by assignment).  Up to
+// the host's limit of keys (at most SW_RANK_LDS_KEYS) a workgroup folds into a table of its own in
+// dynamic LDS and merges its non-empty entries into the global table at the end, as k_grid_count does;
+// above it rows go to the global table, a run of equal keys in a wave reduced across its lanes first
+// so that only the run's head issues atomics (profiles/hot_rank/README.md).
+//
+// The global table is SW_RANK_TAB_WORDS arrays of n_keys int64 (count, min key, max key, date, seq).
+
+// b ^ ((b >> 63) & INT64_MAX) of a double's bits: signed order is the IEEE total order of non-NaN
+// doubles (-0.0 below +0.0).  Its own inverse.
+__device__ __forceinline__ int64_t rank_key(int64_t b) { return b ^ ((b >> 63) & INT64_MAX); }
+
+enum { RANK_NO = 0, RANK_NAN = 1, RANK_UNGROUPED = 2, RANK_GROUPED = 3 };
+
+// The row's class; for a grouped row *key (inside [0, n_keys)), *d and *vk (its value's rank key, 0 for a
+// type without values) are set.
+__device__ __forceinline__ int rank_candidate(const SwRankQuery& q, int64_t r, int64_t* key, int64_t* d, int64_t* vk) {
+  int32_t a;
+  if (!ring_row_test(q.ring, r, (uint8_t)q.event_type, &a, d)) return RANK_NO;
+  if (q.name_on && (int64_t)q.name[r] != q.name_hash) return RANK_NO;
+  if (q.min_level >= 0 && (int64_t)q.level[r] < q.min_level) return RANK_NO;
+  *vk = 0;
+  if (q.event_type == SW_EV_MEASUREMENT) {
+    const double v = q.v0[r];
+    if (v != v) return RANK_NAN;
+    *vk = rank_key(__double_as_longlong(v));
+  }
+  const int64_t k = q.key[r];
+  if (k < 0 || k >= q.n_keys) return RANK_UNGROUPED;      // what keeps a key inside the tables
+  *key = k;
+  return RANK_GROUPED;
+}
+
+__global__ __launch_bounds__(BLK) void k_rank_init(int64_t* __restrict__ tab, int64_t n_keys) {
+  const int64_t i = (int64_t)BID * BLK + threadIdx.x;   // the launch covers n_keys <= SW_RANK_MAX_KEYS
+  if (i < n_keys) {
+    tab[i] = 0;
+    tab[n_keys + i] = INT64_MAX;
+    tab[2 * n_keys + i] = INT64_MIN;
+    tab[3 * n_keys + i] = INT64_MIN;
+    tab[4 * n_keys + i] = INT64_MIN;
+  }
+}
+
+// n rows of one key into the global table: the plain read ahead of each max / min is k_near_best's.
+__device__ __forceinline__ void rank_fold_global(int64_t* __restrict__ tab, int64_t n_keys, int64_t key, uint32_t n,
+                                                 bool values, int64_t lo, int64_t hi, int64_t d) {
+  atomicAdd((ull*)&tab[key], (ull)n);
+  if (values) {
+    if (tab[n_keys + key] > lo) atomicMin((long long*)&tab[n_keys + key], (long long)lo);
+    if (tab[2 * n_keys + key] < hi) atomicMax((long long*)&tab[2 * n_keys + key], (long long)hi);
+  }
+  if (tab[3 * n_keys + key] < d) atomicMax((long long*)&tab[3 * n_keys + key], (long long)d);
+}
+
+// counters: [0] candidates, [1] NaN measurements, [2] ungrouped rows ([3]: k_rank_emit's groups).
+// LDS: 28 B of dynamic LDS per key, the three int64 arrays first.  COMBINE (global form only): runs of
+// equal keys in a wave are reduced across lanes and only their heads issue atomics.
+template <bool LDS, bool COMBINE>
+__global__ __launch_bounds__(BLK) void k_rank_fold(const SwRankQuery q, int64_t* __restrict__ tab,
+                                                   uint32_t* __restrict__ counters) {
+  extern __shared__ int64_t rank_tab[];
+  const int64_t nk = q.n_keys;
+  const bool values = q.event_type == SW_EV_MEASUREMENT;
+  int64_t* const l_min = rank_tab;
+  int64_t* const l_max = rank_tab + nk;
+  int64_t* const l_date = rank_tab + 2 * nk;
+  uint32_t* const l_count = (uint32_t*)(rank_tab + 3 * nk);
+  if constexpr (LDS) {
+    for (uint32_t c = threadIdx.x; c < (uint32_t)nk; c += BLK) {
+      l_min[c] = INT64_MAX;
+      l_max[c] = INT64_MIN;
+      l_date[c] = INT64_MIN;
+      l_count[c] = 0;
+    }
+    __syncthreads();
+  }
+  uint32_t n_cand = 0, n_nan = 0, n_ung = 0;
+  const int64_t stride = (int64_t)gridDim.x * BLK;
+  // whole waves take every turn (the ballots and shuffles need them); a row past the ring is no candidate
+  for (int64_t r0 = (int64_t)BID * BLK; r0 < q.ring.n_rows; r0 += stride) {
+    const int64_t r = r0 + threadIdx.x;
+    int64_t key = -1, d = 0, vk = 0;
+    const int cls = rank_candidate(q, r, &key, &d, &vk);
+    const bool in = cls == RANK_GROUPED;
+    n_cand += (uint32_t)__popcll(__ballot(cls != RANK_NO));
+    n_nan += (uint32_t)__popcll(__ballot(cls == RANK_NAN));
+    n_ung += (uint32_t)__popcll(__ballot(cls == RANK_UNGROUPED));
+    if constexpr (LDS) {
+      if (in) {
+        atomicAdd(&l_count[key], 1u);             // a workgroup's rows: under 2^32
+        if (values) {
+          atomicMin((long long*)&l_min[key], (long long)vk);
+          atomicMax((long long*)&l_max[key], (long long)vk);
+        }
+        atomicMax((long long*)&l_date[key], (long long)d);
+      }
+    } else if constexpr (COMBINE) {
+      const ull grouped = __ballot(in);
+      if (!grouped) continue;                     // the whole wave
+      // a grouped lane whose left neighbour is grouped with the same key belongs to that neighbour's run;
+      // a lane past the ring or of another class is not grouped, so it ends the run on its left
+      const int lane = (int)lane_id();
+      const int64_t left = __shfl_up(key, 1, 64);                 // key is -1 unless grouped
+      const bool head = in && (lane == 0 || left != key);
+      const ull heads = __ballot(head);
+      uint32_t n = 1;
+      int64_t lo = vk, hi = vk, dd = d;
+      if (heads != grouped) {                     // some run is longer than one lane
+        // the run's end: the next head or lane that is not grouped, above this lane
+        const ull stops = (heads | ~grouped) & ~((2ull << lane) - 1ull);
+        const int end = stops ? (int)__ffsll((long long)stops) - 1 : 64;
+        for (int off = 1; off < 64; off <<= 1) {                  // lane l holds its run's [l, min(l + off, end))
+          const uint32_t n2 = __shfl_down(n, off, 64);
+          const int64_t lo2 = __shfl_down(lo, off, 64), hi2 = __shfl_down(hi, off, 64), d2 = __shfl_down(dd, off, 64);
+          if (lane + off < end) {
+            n += n2;
+            lo = lo2 < lo ? lo2 : lo;
+            hi = hi2 > hi ? hi2 : hi;
+            dd = d2 > dd ? d2 : dd;
+          }
+        }
+      }
+      if (head) rank_fold_global(tab, nk, key, n, values, lo, hi, dd);
+    } else {
+      if (in) rank_fold_global(tab, nk, key, 1u, values, vk, vk, d);
+    }
+  }
+  if constexpr (LDS) {
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < (uint32_t)nk; c += BLK) {  // every key of the table, not the first BLK
+      const uint32_t n = l_count[c];
+      if (n) rank_fold_global(tab, nk, c, n, values, l_min[c], l_max[c], l_date[c]);
+    }
+  }
+  if (lane_id() == 0) {
+    if (n_cand) atomicAdd(&counters[0], n_cand);
+    if (n_nan) atomicAdd(&counters[1], n_nan);
+    if (n_ung) atomicAdd(&counters[2], n_ung);
+  }
+}
+
+// The same test again: a row whose date is its group's newest raises the group's store sequence
+// (k_near_best pass 1).
+__global__ __launch_bounds__(BLK) void k_rank_last(const SwRankQuery q, int64_t* __restrict__ tab) {
+  const int64_t stride = (int64_t)gridDim.x * BLK, nk = q.n_keys;
+  for (int64_t r = (int64_t)BID * BLK + threadIdx.x; r < q.ring.n_rows; r += stride) {
+    int64_t key, d, vk;
+    if (rank_candidate(q, r, &key, &d, &vk) != RANK_GROUPED || tab[3 * nk + key] != d) continue;
+    const int64_t s = ring_seq(q.ring, r);
+    if (tab[4 * nk + key] < s) atomicMax((long long*)&tab[4 * nk + key], (long long)s);
+  }
+}
+
+// Non-empty groups as SwRankCells, compacted in any order (ballot + one atomic per wave that has any)
+// beside the stat's sort key; counters[3] = their number.  `last` is v0 at the ring row of the winning
+// sequence; last_id is left as that sequence.  cells / sort_key hold n_keys entries.
+__global__ __launch_bounds__(BLK) void k_rank_emit(const SwRankQuery q, const int64_t* __restrict__ tab,
+                                                   SwRankCell* __restrict__ cells, int64_t* __restrict__ sort_key,
+                                                   uint32_t* __restrict__ counters) {
+  const int64_t i = (int64_t)BID * BLK + threadIdx.x, nk = q.n_keys;   // the launch covers n_keys
+  const int64_t n = i < nk ? tab[i] : 0;
+  const ull mask = __ballot(n > 0);
+  if (!mask) return;
+  uint32_t base = 0;
+  if (lane_id() == 0) base = atomicAdd(&counters[3], (uint32_t)__popcll(mask));
+  base = __shfl(base, 0, 64);
+  if (n <= 0) return;
+  const bool values = q.event_type == SW_EV_MEASUREMENT;
+  SwRankCell c;
+  c.key = i;
+  c.count = n;
+  c.last_date = tab[3 * nk + i];
+  c.last_id = tab[4 * nk + i];
+  int64_t last_key = 0;
+  c.min = c.max = c.last = 0.0;
+  if (values) {
+    const SwRingView& v = q.ring;
+    int64_t row = c.last_id - v.seq0 + v.head;                   // ring_seq the other way round
+    if (row >= v.n_rows) row -= v.n_rows;
+    c.min = __longlong_as_double(rank_key(tab[nk + i]));
+    c.max = __longlong_as_double(rank_key(tab[2 * nk + i]));
+    if (row >= 0 && row < v.n_rows) {                            // always, once k_rank_last has run
+      c.last = q.v0[row];
+      last_key = rank_key(__double_as_longlong(c.last));
+    }
+  }
+  const uint32_t pos = base + (uint32_t)__popcll(mask & lanemask_lt());
+  cells[pos] = c;
+  sort_key[pos] = q.stat == SW_RANK_MIN ? tab[nk + i] : q.stat == SW_RANK_MAX ? tab[2 * nk + i]
+                  : q.stat == SW_RANK_LAST ? last_key : n;
 }
 
 // ============================================================================ reject refs
@@ -2827,6 +3027,59 @@ int sw_store_grid(const SwGridQuery* q, SwGridCell* cells, uint32_t* counters, h
   return (int)hipGetLastError();
 }
 
+// The key count up to which sw_store_rank folds in LDS tables: SW_RANK_LDS_KEYS unless lowered here (0:
+// every ranking goes straight to the global table), which profiles/hot_rank measures against.
+// keys < 0: no change.  Returns the limit in force.
+static int64_t rank_lds_keys = SW_RANK_LDS_KEYS;
+int64_t sw_rank_lds_keys(int64_t keys) {
+  if (keys >= 0) rank_lds_keys = keys < SW_RANK_LDS_KEYS ? keys : SW_RANK_LDS_KEYS;
+  return rank_lds_keys;
+}
+
+// Whether the global form reduces a wave's runs of equal keys before its atomics (1, the default) or
+// issues them row by row (0): what profiles/hot_rank measures against.  on < 0: no change.
+static int rank_combine = 1;
+int sw_rank_combine(int on) {
+  if (on >= 0) rank_combine = on != 0;
+  return rank_combine;
+}
+
+// Ranking: tab (int64 [SW_RANK_TAB_WORDS * n_keys]) is set up here; cells and sort_key [n_keys] receive the
+// non-empty groups in any order; counters (u32[4], zeroed here): candidates, NaN measurements,
+// ungrouped rows, groups.  The query is refused, before any launch, unless the event type is one of the
+// four, the key space within SW_RANK_MAX_KEYS, the level within -1..3 and the columns there: what keeps
+// a key inside the tables.  n_keys == 0: every candidate is ungrouped (or NaN); only the counters are written.
+int sw_store_rank(const SwRankQuery* q, int64_t* tab, SwRankCell* cells, int64_t* sort_key, uint32_t* counters,
+                  hipStream_t s) {
+  const SwRingView& v = q->ring;
+  const bool type = q->event_type == SW_EV_MEASUREMENT || q->event_type == SW_EV_LOCATION ||
+                    q->event_type == SW_EV_ALERT || q->event_type == SW_EV_STATE_CHANGE;
+  const bool stat = q->stat == SW_RANK_COUNT ||
+                    (q->stat >= SW_RANK_MIN && q->stat <= SW_RANK_LAST && q->event_type == SW_EV_MEASUREMENT && q->name_on);
+  if (!type || !stat || q->n_keys < 0 || q->n_keys > SW_RANK_MAX_KEYS || q->min_level < -1 || q->min_level > 3 ||
+      (q->min_level >= 0 && q->event_type != SW_EV_ALERT) || !q->level || !q->name || !q->v0 || !q->key || !counters ||
+      (q->n_keys && (!tab || !cells || !sort_key)) || v.start > v.end || v.n_rows < 1 ||
+      v.n_rows > ((int64_t)1 << 32) || v.n_asg < 1 || v.head < 0 || v.head >= v.n_rows)
+    return (int)hipErrorInvalidValue;
+  const int64_t nk = q->n_keys;
+  hipError_t e = hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), s);
+  if (e != hipSuccess) return (int)e;
+  const unsigned gk = (unsigned)((nk + BLK - 1) / BLK);
+  if (nk) k_rank_init<<<gk, BLK, 0, s>>>(tab, nk);
+  const int g = grid_for((v.n_rows + STAGE_U - 1) / STAGE_U);
+  if (nk <= rank_lds_keys)
+    k_rank_fold<true, false><<<g, BLK, (size_t)nk * 28, s>>>(*q, tab, counters);
+  else if (rank_combine)
+    k_rank_fold<false, true><<<g, BLK, 0, s>>>(*q, tab, counters);
+  else
+    k_rank_fold<false, false><<<g, BLK, 0, s>>>(*q, tab, counters);
+  if (nk) {
+    k_rank_last<<<grid_for(v.n_rows), BLK, 0, s>>>(*q, tab);
+    k_rank_emit<<<gk, BLK, 0, s>>>(*q, tab, cells, sort_key, counters);
+  }
+  return (int)hipGetLastError();
+}
+
 int sw_state_lookup(const SwMsSlot* ms, int64_t mask, int32_t asg, int32_t n_ids, SwMsSlot* out, uint32_t* n_out,
                     hipStream_t s) {
   hipError_t e = hipMemsetAsync(n_out, 0, sizeof(uint32_t), s);
@@ -2960,6 +3213,7 @@ int sw_abi_sizes(int64_t* out) {
   out[13] = sizeof(SwSeriesQuery);
   out[14] = sizeof(SwZoneQuery);
   out[15] = sizeof(SwGridQuery);
+  out[16] = sizeof(SwRankQuery);
   return 0;
 }
 

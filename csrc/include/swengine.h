@@ -383,6 +383,50 @@ static_assert(sizeof(SwGridQuery) == 192, "SwGridQuery is 24 8-byte words");
 // and merges it into the global one at the end; above, every row goes to the global table.
 #define SW_GRID_LDS_CELLS 4096
 
+// One group of a ranking over the ring (sw_store_rank; RANK_CELL in sitewhere_amd/models/columnar.py
+// mirrors it).  min / max / last: of the group's v0, 0.0 for an event type that has no value; last_date /
+// last_id: the group's row with the largest (date, event id).  The device writes that row's store
+// sequence into last_id; the engine turns it into an event id.
+typedef struct SwRankCell {
+  int64_t key;
+  int64_t count;
+  double min, max, last;
+  int64_t last_date, last_id;
+} SwRankCell;
+static_assert(sizeof(SwRankCell) == 56, "SwRankCell is seven 8-byte words");
+
+// A ranking query (sw_store_rank; RANK_QUERY names the words).  A candidate is a row that passes the
+// ring's row test, whose name is name_hash when name_on and whose level is at least min_level when that
+// is not negative; it folds into group key[r] when that lies in [0, n_keys).
+typedef struct SwRankQuery {
+  SwRingView ring;
+  const uint8_t* level;        // ring columns
+  const uint64_t* name;
+  const double* v0;
+  const int32_t* key;          // the group column: asg, cust, area or asset
+  int64_t event_type;          // SW_EV_MEASUREMENT (the only one whose v0 is read), _LOCATION, _ALERT, _STATE_CHANGE
+  int64_t name_on;
+  int64_t name_hash;           // the name column's bits
+  int64_t min_level;           // -1: any
+  int64_t n_keys;              // 0 .. SW_RANK_MAX_KEYS
+  int64_t stat;                // SW_RANK_COUNT ..: what k_rank_emit writes as the sort key
+} SwRankQuery;
+static_assert(sizeof(SwRankQuery) == 160, "SwRankQuery is 20 8-byte words");
+
+enum { SW_RANK_COUNT = 0, SW_RANK_MIN = 1, SW_RANK_MAX = 2, SW_RANK_LAST = 3 };
+
+#define SW_RANK_MAX_KEYS (1 << 22)
+// The device's fold table: SW_RANK_TAB_WORDS int64 arrays of n_keys each -- count, smallest and largest
+// rank key of v0, newest date, largest store sequence at that date.
+#define SW_RANK_TAB_WORDS 5
+// Up to this many keys a workgroup of k_rank_fold folds into a table of its own in LDS and merges it
+// into the global one at the end; above, rows go to the global table.  An entry is 28 B (a uint32 count
+// and three int64), and the table is sized by the query's key space, not by the limit: the few-key
+// dimensions this form is for (customers, areas, assets) leave a CU's 160 KB free for full occupancy;
+// at the limit a table is 56 KB, inside the 64 KB a workgroup gets without opting in, and two workgroups
+// (8 waves) share a CU, which still beats every row's atomics meeting on a few global addresses.
+#define SW_RANK_LDS_KEYS 2048
+
 #define SW_N_STATS 24
 
 enum {

@@ -362,3 +362,10 @@ class SiteWhereClient:
         "count", "lastDate"}``, with ``numResults``, ``outside``, ``invalid`` and the cell steps."""
         return self.get(f"/search/{provider_id}/locations/grid", latMin=lat_min, latMax=lat_max, lonMin=lon_min,
                         lonMax=lon_max, rows=rows, cols=cols, **crit)
+
+    def event_ranking(self, event_type: str, group_by: str, provider_id: str = "events", **crit):
+        """Assignments, customers, areas or assets ranked by a statistic of their events (``stat``: ``count``,
+        or ``min`` / ``max`` / ``last`` of ``measurementId``; ``top``; ``alertType``, ``minLevel``;
+        ``startDate`` / ``endDate``; ``ascending``).  ``{"numResults", "nan", "ungrouped", "groups",
+        "results"}``, ``results`` as ``{"id", "count", "min", "max", "last", "lastDate"}``."""
+        return self.get(f"/search/{provider_id}/events/ranking", eventType=event_type, groupBy=group_by, **crit)

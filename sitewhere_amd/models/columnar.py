@@ -160,6 +160,15 @@ GRID_WORDS = ("v0", "v1", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "d_lat", "d_lo
               "latest", "best_date", "best_seq")
 GRID_QUERY = RING_QUERY + GRID_WORDS
 GRID_QUERY_F64 = ("lat_lo", "lat_hi", "lon_lo", "lon_hi", "d_lat", "d_lon")
+# One group of a ranking over the ring (SwRankCell in swengine.h): its key, its rows, min / max / last of
+# their v0 (0.0 for a type that has no value) and the (date, event id) of its newest row.
+RANK_CELL = np.dtype([("key", "<i8"), ("count", "<i8"), ("min", "<f8"), ("max", "<f8"), ("last", "<f8"),
+                      ("last_date", "<i8"), ("last_id", "<i8")])
+assert RANK_CELL.itemsize == 56
+# The int64 words of a ranking query (SwRankQuery in swengine.h), in order.
+RANK_QUERY = RING_QUERY + ("level", "name", "v0", "key", "event_type", "name_on", "name_hash", "min_level", "n_keys",
+                           "stat")
+RANK_MAX_KEYS = 1 << 22        # SW_RANK_MAX_KEYS
 
 # Durable-block encoder state (u64 words): the result words follow the max_pages look-back words
 # (SEG_ST_* in swseg.h) -- block bytes (~0 on error), errors, store sequence of the first row.

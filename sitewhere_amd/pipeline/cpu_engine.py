@@ -741,6 +741,27 @@ class CpuInboundEngine(EngineBase):
         return cells, {"candidates": len(rows), "invalid": n_invalid, "outside": n_outside,
                        "hot_since": self._hot_since(self.cursor)}
 
+    def rank_store(self, event_type, group, stat="count", k=10, asg_idx=None, start=None, end=None, name_hash=None,
+                   min_level=None, ascending=False):
+        """The oracle of the MI355X ranking kernels: a numpy filter, then ``rank.rank_select`` over every
+        candidate."""
+        from .rank import check_rank_args, rank_select
+        event_type, k, name_hash, min_level = check_rank_args(event_type, group, stat, k, start, end, name_hash, min_level)
+        col, n_keys = self.rank_key_space(group)
+        s = self.store
+        rows, d, seq = self._ring_candidates(event_type, asg_idx, start, end)
+        keep = np.ones(len(rows), bool)
+        if name_hash is not None:
+            keep &= s["name"][rows] == np.uint64(name_hash)
+        if min_level is not None:
+            keep &= s["level"][rows] >= min_level
+        rows, d, seq = rows[keep], d[keep], seq[keep]
+        cells, n_rows, n_nan, n_ungrouped, groups = rank_select(
+            s[col][rows], d, seq * self.world + self.rank, s["v0"][rows] if event_type == EV_MEASUREMENT else None,
+            n_keys, stat, k, bool(ascending))
+        return cells, {"candidates": len(rows), "rows": n_rows, "nan": n_nan, "ungrouped": n_ungrouped,
+                       "groups": groups, "hot_since": self._hot_since(self.cursor)}
+
     def intern_table(self) -> dict:
         """name hash -> dense name id (same form as the GPU and native engines)."""
         return dict(self.intern)

@@ -533,6 +533,60 @@ class EngineBase:
         that is not finite, or ``start > end``."""
         raise NotImplementedError
 
+    def rank_store(self, event_type: int, group: str, stat: str = "count", k: int | None = 10, asg_idx=None,
+                   start: int | None = None, end: int | None = None, name_hash: int | None = None,
+                   min_level: int | None = None, ascending: bool = False):
+        """The groups of this shard's ring rows of ``event_type`` (``EV_MEASUREMENT``, ``EV_LOCATION``,
+        ``EV_ALERT`` or ``EV_STATE_CHANGE``) ranked by a statistic: which devices report the highest
+        temperature, which customers raise the most alerts at warning level or above, which areas have
+        gone quiet.  ``group``: ``"assignment" | "customer" | "area" | "asset"``; a row's key is its ring
+        column ``asg`` / ``cust`` / ``area`` / ``asset``, the context it was persisted with.  The key space
+        ``n_keys`` (:meth:`rank_key_space`) is ``cfg.max_assignments`` for assignments and, for a context
+        dimension, the largest id any assignment carries now plus 1 (0 when none has one); more than
+        ``RANK_MAX_KEYS`` (1 << 22) is a ``ValueError``.
+
+        ``stat``: ``"count"`` for any type; ``"min" | "max" | "last"`` (of ``v0``) need ``EV_MEASUREMENT``
+        and a ``name_hash``, since a value ranking across different names means nothing.  ``k``: an integer
+        >= 1, or None for every non-empty group.  ``min_level``: alerts only, 0..3.
+
+        A row is a candidate when it passes the shared row test (type, ``asg_idx`` -- None: every
+        assignment --, date in [start, end], None: that side open), its name equals ``name_hash`` when given
+        and its level is at least ``min_level`` when given.  A candidate is then, in this order: a
+        measurement whose ``v0`` is NaN, counted in ``nan`` as the series query does; a row whose key lies
+        outside [0, n_keys) -- no customer, or an id no assignment carries any more --, counted in
+        ``ungrouped``; else folded into its group.
+
+        Values are ordered by one integer key, ``rank_key(v) = b ^ ((b >> 63) & INT64_MAX)`` of the
+        double's bits as int64 (arithmetic shift; ``pipeline/rank.py``): signed order is the IEEE total
+        order of non-NaN doubles, so -0.0 ranks below +0.0 and min / max return exactly the bits some row
+        holds.  Non-empty groups are ordered by ``stat`` descending (``ascending``: ascending), ties by key
+        ascending; ``count`` compares as an integer, the value statistics by ``rank_key``.
+
+        Returns (cells, info).  ``cells``: a ``RANK_CELL`` array of the first ``k`` groups -- ``key``,
+        ``count``, ``min``, ``max``, ``last`` (the ``v0`` of the group's row with the largest (date, event
+        id)), ``last_date`` and ``last_id`` of that row; min / max / last are 0.0 for a type other than
+        measurements.  ``info`` = ``{"candidates", "rows", "nan", "ungrouped", "groups", "hot_since"}``:
+        ``groups`` is the number of non-empty groups before the cut, ``hot_since`` as in
+        :meth:`aggregate_store`.  Conservation: ``rows + nan + ungrouped == candidates`` and, with ``k``
+        None, ``cells["count"].sum() == rows``.  There is no band: every operation is on integers or copies
+        bits, so every engine answers with the same bytes, on every call.  ``ValueError``
+        (``pipeline/rank.py: check_rank_args``) for anything else, ``start > end`` and ``min_level`` on a
+        type other than alerts included."""
+        raise NotImplementedError
+
+    def rank_key_space(self, group: str) -> tuple[str, int]:
+        """(ring column, ``n_keys``) of a :meth:`rank_store` group; ``ValueError`` past ``RANK_MAX_KEYS``."""
+        from .rank import RANK_MAX_KEYS
+        if group == "assignment":
+            col, n = "asg", int(self.cfg.max_assignments)
+        else:
+            col, ids = {"customer": ("cust", self.asg_customer), "area": ("area", self.asg_area),
+                        "asset": ("asset", self.asg_asset)}[group]
+            n = max(int(ids.max()) + 1, 0) if len(ids) else 0       # ids are -1 where an assignment has none
+        if n > RANK_MAX_KEYS:
+            raise ValueError(f"a ranking has at most {RANK_MAX_KEYS} keys")
+        return col, n
+
     @staticmethod
     def _window(page_number: int, page_size: int, total: int) -> tuple[int, int]:
         if page_size <= 0:

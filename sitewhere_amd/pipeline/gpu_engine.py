@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .._native import gpu_gil as gpu_lib
-from ..models.columnar import (EVENT_REC, GRID_CELL, GRID_QUERY_F64, GRID_WORDS, N_STATS, NEAR_QUERY, NEAR_QUERY_F64,
+from ..models.columnar import (EVENT_REC, RANK_CELL, RANK_QUERY, GRID_CELL, GRID_QUERY_F64, GRID_WORDS, N_STATS, NEAR_QUERY, NEAR_QUERY_F64,
                                OUT_REC, NAME_REF, OUT_REC_SIZE, RING_QUERY, SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK, SC_N_OUT,
                                SC_N_RECS, SC_N_REJ, SC_N_RULE, SC_N_WORK, SC_NAMES, SC_OVERFLOW, SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, SERIES_CELL, SERIES_QUERY,
                                ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC, ZONE_QUERY, ZONE_QUERY_F64)
@@ -1560,6 +1560,57 @@ class GpuInboundEngine(EngineBase):
         cells = table[:2 * n_rows * n_cols].cpu().numpy().view(GRID_CELL).reshape(n_rows, n_cols)
         info["candidates"], info["invalid"], info["outside"] = (int(x) for x in counters[:3].cpu().numpy().view(np.uint32))
         cells["last_date"][cells["count"] == 0] = 0                              # the device leaves INT64_MIN there
+        return cells, info
+
+    def rank_store(self, event_type, group, stat="count", k=10, asg_idx=None, start=None, end=None, name_hash=None,
+                   min_level=None, ascending=False):
+        """A ranking of groups on the MI355X (``sw_store_rank``, csrc/hip/swgpu.hip): ``k_rank_fold``
+        makes one pass over the HBM ring and folds each candidate into its group's count, smallest and
+        largest ``rank_key`` and newest date -- in a table per workgroup in LDS, merged into the global one
+        at the end, while the key space has at most ``SW_RANK_LDS_KEYS`` keys, else in the global table --,
+        ``k_rank_last`` finds each group's newest row and ``k_rank_emit`` compacts the non-empty groups
+        into cells beside the statistic's sort key.  The groups are ordered on the device (stable sorts,
+        least significant key first, as ``_order_page`` does) and only ``min(k, groups)`` cells and four
+        counters cross PCIe.  Integer atomics only, so an unchanged ring gives the same bytes every time.
+        Runs on the caller's current stream in buffers of its own, outside the captured step graph; holds
+        the engine lock like :meth:`query_store`."""
+        from .rank import check_rank_args
+        event_type, k, name_hash, min_level = check_rank_args(event_type, group, stat, k, start, end, name_hash, min_level)
+        with self._lock:
+            return self._rank_store(event_type, group, stat, k, asg_idx, start, end, name_hash, min_level, bool(ascending))
+
+    def _rank_store(self, event_type, group, stat, k, asg_idx, start, end, name_hash, min_level, ascending):
+        from .rank import RANK_STATS
+        col, n_keys = self.rank_key_space(group)
+        st = self.store
+        info = {"candidates": 0, "rows": 0, "nan": 0, "ungrouped": 0, "groups": 0, "hot_since": None}
+        cur, view, bits = self._ring_view(asg_idx, start, end)
+        if view["n_rows"] == 0:
+            return np.zeros(0, RANK_CELL), info                                  # no launch
+        info["hot_since"] = self._hot_since(cur)
+        buf = functools.partial(self._ring_buf, "rank")
+        name = 0 if name_hash is None else name_hash - (1 << 64) if name_hash >= 1 << 63 else name_hash
+        q = self._query_words(RANK_QUERY, (), dict(
+            view, level=_ptr(st["level"]), name=_ptr(st["name"]), v0=_ptr(st["v0"]), key=_ptr(st[col]),
+            event_type=event_type, name_on=int(name_hash is not None), name_hash=name,
+            min_level=-1 if min_level is None else min_level, n_keys=n_keys, stat=RANK_STATS.index(stat)))
+        counters = buf("counters", 4)
+        tab = buf("tab", 5 * max(n_keys, 1), torch.int64)
+        table = buf("cells", 7 * max(n_keys, 1), torch.int64)
+        sort_key = buf("sort", max(n_keys, 1), torch.int64)
+        _chk(self.lib.sw_store_rank(q.ctypes.data, _ptr(tab), _ptr(table), _ptr(sort_key), _ptr(counters),
+                                    self._stream()), "sw_store_rank")
+        info["candidates"], info["nan"], info["ungrouped"], groups = (
+            int(x) for x in counters[:4].cpu().numpy().view(np.uint32))
+        info["groups"] = groups
+        # stable sorts, least significant key first: key asc, then the statistic
+        rows = table[:7 * groups].view(-1, 7)
+        o = torch.sort(rows[:, 0], stable=True).indices
+        o2 = torch.sort(sort_key[:groups][o], descending=not ascending, stable=True).indices
+        total = rows[:, 1].sum()
+        cells = rows[o[o2[:k]]].cpu().numpy().reshape(-1).view(RANK_CELL)
+        info["rows"] = int(total.item())
+        cells["last_id"] = cells["last_id"] * self.world + self.rank             # the device wrote store sequences
         return cells, info
 
     @staticmethod

@@ -1421,6 +1421,43 @@ class GpuInboundApi:
         cells, info = e.engine.grid_store(*box, n_rows, n_cols, asg, start_date, end_date, latest)
         return grid_response(cells, info, box, info["hot_since"])
 
+    def event_ranking_hot(self, event_type: str, group_by: str, stat: str = "count", top: int | None = 10,
+                          measurement_id: str | None = None, alert_type: str | None = None,
+                          min_level: int | None = None, start_date: int | None = None, end_date: int | None = None,
+                          ascending: bool = False) -> dict:
+        """The tenant's assignments, customers, areas or assets ranked by a statistic of their events in
+        the engine's event ring (``EngineBase.rank_store``: on the MI355X the scan, the group-by and the
+        ordering run in HBM and only the first ``top`` groups cross PCIe).  ``event_type``:
+        ``"Measurement" | "Location" | "Alert" | "StateChange"``; ``group_by``: ``"Assignment" | "Customer" |
+        "Area" | "Asset"``; ``stat``: ``"count"``, or ``"min" | "max" | "last"`` of the measurement
+        ``measurement_id``; ``alert_type`` / ``min_level`` (0..3) narrow alerts; ``top`` None: every group.
+        Returns ``{"hotSince", "numResults", "nan", "ungrouped", "groups", "results"}``
+        (``pipeline/rank.py: rank_response``), ``results`` as ``{"id", "count", "min", "max", "last",
+        "lastDate"}`` with the entity's id; a group whose key no current assignment carries is left out, as
+        :meth:`list_hot_events` leaves out rows of unknown assignments.  ``hotSince`` as in
+        :meth:`locations_near_hot`.  ``ValueError`` for arguments ``rank_store`` refuses."""
+        from ..pipeline.fleet import hash64
+        from ..pipeline.rank import check_rank_args, rank_response
+        e = self._e
+        if event_type not in self._ETYPE or group_by not in self._INDEX:
+            raise ValueError("eventType must be Measurement, Location, Alert or StateChange and groupBy Assignment, "
+                             "Customer, Area or Asset")
+        et, group = self._ETYPE[event_type], group_by.lower()
+        if (measurement_id is not None and et != EV_MEASUREMENT) or (alert_type is not None and et != EV_ALERT):
+            raise ValueError("measurementId is for measurements and alertType for alerts")
+        name = measurement_id if et == EV_MEASUREMENT else alert_type
+        name_hash = None if name is None else hash64(name)
+        check_rank_args(et, group, stat, top, start_date, end_date, name_hash, min_level)
+        cells, info = e.engine.rank_store(et, group, stat, top, None, start_date, end_date, name_hash, min_level, ascending)
+        pos = self._INDEX[group_by]
+        with e._lock:
+            ctx = e.engine.ctx_table()
+            entity = {}
+            for ai, a in e._asg_entities.items():
+                key = ai if pos == 0 else int(ctx[ai, pos - 1])
+                entity.setdefault(key, (a.id, a.device_id, a.customer_id, a.area_id, a.asset_id)[pos])
+        return rank_response(cells, info, [entity.get(int(c["key"])) for c in cells], info["hot_since"])
+
     def measurement_series_hot(self, index: str, entity_ids: list, measurement_ids: list | None, start_date: int,
                                end_date: int, bucket_ms: int) -> dict:
         """Measurement series in time buckets from the engine's event ring

@@ -333,6 +333,12 @@ class InboundProcessingApi:
         engine keeps none, so None -- the caller counts event management's list instead."""
         return None
 
+    def event_ranking_hot(self, event_type, group_by, stat="count", top=10, measurement_id=None, alert_type=None,
+                          min_level=None, start_date=None, end_date=None, ascending=False):
+        """A ranking of groups from a hot store (``GpuInboundApi.event_ranking_hot``): the per-event
+        engine keeps none, so None -- the caller ranks event management's list instead."""
+        return None
+
 
 class InboundProcessingMicroservice(MultitenantMicroservice):
     identifier = "inbound-processing"

@@ -187,6 +187,37 @@ class SolrSearchProvider:
         return {"hotSince": None, "numResults": 0, "outside": 0, "invalid": 0, "rows": rows, "cols": cols,
                 "latStep": d_lat, "lonStep": d_lon, "cells": []}
 
+    def get_event_ranking(self, criteria=None) -> dict:
+        """No aggregation is sent to Solr: an empty ranking, once the arguments are checked."""
+        _rank_criteria(criteria)
+        return {"hotSince": None, "numResults": 0, "nan": 0, "ungrouped": 0, "groups": 0, "results": []}
+
+
+_RANK_TYPES = {"Measurement": 0, "Location": 1, "Alert": 2, "StateChange": 5}    # EV_* of models/columnar.py
+_RANK_LISTS = {"Measurement": "list_measurements_for_index", "Location": "list_locations_for_index",
+               "Alert": "list_alerts_for_index", "StateChange": "list_state_changes_for_index"}
+
+
+def _rank_criteria(criteria):
+    """The ranking criteria, checked (``pipeline/rank.py: check_rank_args``): a dict of the keyword arguments of
+    ``GpuInboundApi.event_ranking_hot``."""
+    from ..pipeline.rank import check_rank_args
+    c = criteria or {}
+    et, group = c.get("eventType"), c.get("groupBy")
+    if et not in _RANK_TYPES or group not in ("Assignment", "Customer", "Area", "Asset"):
+        raise ValueError("eventType must be Measurement, Location, Alert or StateChange and groupBy Assignment, "
+                         "Customer, Area or Asset")
+    mx, al = c.get("measurementId"), c.get("alertType")
+    if (mx is not None and et != "Measurement") or (al is not None and et != "Alert"):
+        raise ValueError("measurementId is for measurements and alertType for alerts")
+    name = mx if et == "Measurement" else al
+    args = dict(event_type=et, group_by=group, stat=c.get("stat") or "count", top=c.get("top", 10), measurement_id=mx,
+                alert_type=al, min_level=c.get("minLevel"), start_date=c.get("startDate"), end_date=c.get("endDate"),
+                ascending=bool(c.get("ascending", False)))
+    check_rank_args(_RANK_TYPES[et], group.lower(), args["stat"], args["top"], args["start_date"], args["end_date"],
+                    None if name is None else 0, args["min_level"])
+    return args
+
 
 class EventStoreSearchProvider:
     """In-process provider: ``field:value`` terms (AND) over the tenant's event store."""
@@ -303,6 +334,32 @@ class EventStoreSearchProvider:
             {"pageNumber": 1, "pageSize": 0, "startDate": start, "endDate": end}).results
         return host_grid(locs, *box, rows, cols, start, end, latest)
 
+    def get_event_ranking(self, criteria=None) -> dict:
+        """The tenant's assignments, customers, areas or assets ranked by a statistic of their events
+        (``EngineBase.rank_store`` has the contract).  ``criteria``: a dict of ``eventType`` (``Measurement``,
+        ``Location``, ``Alert``, ``StateChange``), ``groupBy`` (``Assignment``, ``Customer``, ``Area``,
+        ``Asset``) and optionally ``stat`` (``count``; ``min``, ``max``, ``last`` of ``measurementId``),
+        ``top`` (None: every group), ``measurementId``, ``alertType``, ``minLevel``, ``startDate``,
+        ``endDate`` and ``ascending``.  Served from the inbound engine's event ring when the tenant has one
+        and the ring covers the range, by :meth:`get_locations_grid`'s rule, else from event management's
+        list of the range's events, ranked on the host by the same function (``pipeline/rank.py``).
+        Returns ``{"hotSince", "numResults", "nan", "ungrouped", "groups", "results"}`` on both routes;
+        ``ValueError`` for arguments out of range or ``startDate > endDate``."""
+        from ..pipeline.rank import host_rank
+        a = _rank_criteria(criteria)
+        start, end = a["start_date"], a["end_date"]
+        token = self._e.tenant.token
+        hot = self._e.ms.api("InboundProcessing", token).event_ranking_hot(**a)
+        if hot is not None and (hot["hotSince"] is None or (start is not None and start >= hot["hotSince"])):
+            return hot
+        asgs = self._e.ms.api("DeviceManagement", token).list_device_assignments({"pageNumber": 1, "pageSize": 0})
+        lister = getattr(self._e.ms.api("DeviceEventManagement", token), _RANK_LISTS[a["event_type"]])
+        evs = lister("Assignment", [x.id for x in asgs.results],
+                     {"pageNumber": 1, "pageSize": 0, "startDate": start, "endDate": end}).results
+        name = a["measurement_id"] if a["event_type"] == "Measurement" else a["alert_type"]
+        return host_rank(evs, _RANK_TYPES[a["event_type"]], a["group_by"].lower(), a["stat"], a["top"], start, end, name,
+                         a["min_level"], a["ascending"])
+
 
 class SearchProviderManager:
     def __init__(self, providers: dict):
@@ -338,6 +395,13 @@ class SearchProviderManager:
         if p is None:
             raise NotFoundException(ErrorCode.Error, f"search provider {provider_id}")
         return p.get_locations_grid(criteria)
+
+    def get_event_ranking(self, provider_id: str, criteria=None) -> dict:
+        """A ranking of groups by their events on one provider (see the providers' methods)."""
+        p = self._p.get(provider_id)
+        if p is None:
+            raise NotFoundException(ErrorCode.Error, f"search provider {provider_id}")
+        return p.get_event_ranking(criteria)
 
 
 class EventSearchTenantEngine(MicroserviceTenantEngine):

@@ -934,6 +934,22 @@ def misc_router(web: WebRest) -> APIRouter:
             raise SiteWhereSystemException(ErrorCode.IncompleteData, detail=str(e)) from None
         return res
 
+    @r.get("/search/{providerId}/events/ranking")
+    def events_ranking(providerId: str, eventType: str, groupBy: str, stat: str = "count", top: int | None = 10,
+                       measurementId: str | None = None, alertType: str | None = None, minLevel: int | None = None,
+                       startDate: str | None = None, endDate: str | None = None, ascending: bool = False,
+                       c: Ctx = TENANT):
+        """Assignments, customers, areas or assets ranked by a statistic of their events: the count, or the
+        min / max / last value of one measurement; ``top`` groups, largest first unless ``ascending``.  An
+        addition over the reference."""
+        crit = dict(date_paging(1, 0, startDate, endDate), eventType=eventType, groupBy=groupBy, stat=stat, top=top,
+                    measurementId=measurementId, alertType=alertType, minLevel=minLevel, ascending=ascending)
+        try:
+            res = c.svc("EventSearch").get_event_ranking(providerId, crit)
+        except ValueError as e:
+            raise SiteWhereSystemException(ErrorCode.IncompleteData, detail=str(e)) from None
+        return res
+
     # system -----------------------------------------------------------------------------
     @r.get("/system/version")
     def version(c: Ctx = GLOBAL):
