@@ -1971,17 +1971,37 @@ __global__ __launch_bounds__(BLK) void k_series_carry(const SwSeriesCell* __rest
 // if it is that one.  No floating-point atomics.
 enum { NEAR_NO = 0, NEAR_INVALID = 1, NEAR_VALID = 2 };
 
-// The row's class; for a candidate (valid or not) *a, *d, *lat, *lon are its columns.  Q: SwNearQuery,
-// SwZoneQuery or SwGridQuery (ring, v0, v1).
-template <class Q>
-__device__ __forceinline__ int near_candidate(const Q& q, int64_t r, int32_t* a, int64_t* d, double* lat,
+// The row's class; for a candidate (valid or not) *a, *d, *lat, *lon are its columns.
+__device__ __forceinline__ int near_candidate(const SwPositionView& p, int64_t r, int32_t* a, int64_t* d, double* lat,
                                               double* lon) {
-  if (!ring_row_test(q.ring, r, (uint8_t)SW_EV_LOCATION, a, d)) return NEAR_NO;
-  *lat = q.v0[r];
-  *lon = q.v1[r];
+  if (!ring_row_test(p.ring, r, (uint8_t)SW_EV_LOCATION, a, d)) return NEAR_NO;
+  *lat = p.v0[r];
+  *lon = p.v1[r];
   // written so that a NaN fails: not finite, or outside [-90, 90] x [-180, 180]
   return (fabs(*lat) <= 90.0 && fabs(*lon) <= 180.0) ? NEAR_VALID : NEAR_INVALID;
 }
+
+// Whether a query looks at row r of class cls, assignment a and date d: a valid candidate and, with
+// `latest`, the one k_near_best left in the two tables.
+__device__ __forceinline__ bool position_looked(const SwPositionView& p, int cls, int64_t r, int32_t a, int64_t d) {
+  return cls == NEAR_VALID && (!p.latest || (p.best_date[a] == d && p.best_seq[a] == ring_seq(p.ring, r)));
+}
+
+// A wave's candidates and invalid candidates: count() on every turn, whole waves calling (rows past the
+// ring too), then flush() adds them to counters[at] and counters[at + 1].
+struct PositionCounts {
+  uint32_t n_cand = 0, n_bad = 0;
+  __device__ __forceinline__ void count(int cls) {
+    n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
+    n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
+  }
+  __device__ __forceinline__ void flush(uint32_t* __restrict__ counters, int at) const {
+    if (lane_id() == 0) {
+      if (n_cand) atomicAdd(&counters[at], n_cand);
+      if (n_bad) atomicAdd(&counters[at + 1], n_bad);
+    }
+  }
+};
 
 // core/geo.py haversine_m, operation for operation (no contraction into fma: the numpy oracle has none).
 __device__ __forceinline__ double near_haversine(double p1, double cos_p1, double lon1, double lat2, double lon2) {
@@ -1996,21 +2016,21 @@ __device__ __forceinline__ double near_haversine(double p1, double cos_p1, doubl
 
 // PASS 0: best_date[a] = newest date among a's valid candidates; PASS 1: best_seq[a] = largest store
 // sequence among those at that date.  The plain read ahead of the atomic saves most atomics on a ring
-// that is roughly chronological; a stale read only costs a redundant one.  Q: SwNearQuery, SwZoneQuery
-// or SwGridQuery (what near_candidate reads, best_date, best_seq).
-template <int PASS, class Q>
-__global__ __launch_bounds__(BLK) void k_near_best(const Q q) {
+// that is roughly chronological; a stale read only costs a redundant one.  Both are maxima over the same
+// rows, so running the two passes again over an unchanged ring leaves the tables as they are.
+template <int PASS>
+__global__ __launch_bounds__(BLK) void k_near_best(const SwPositionView p) {
   const int64_t stride = (int64_t)gridDim.x * BLK;
-  for (int64_t r = (int64_t)BID * BLK + threadIdx.x; r < q.ring.n_rows; r += stride) {
+  for (int64_t r = (int64_t)BID * BLK + threadIdx.x; r < p.ring.n_rows; r += stride) {
     int32_t a;
     int64_t d;
     double lat, lon;
-    if (near_candidate(q, r, &a, &d, &lat, &lon) != NEAR_VALID) continue;   // a is inside [0, n_asg) here
+    if (near_candidate(p, r, &a, &d, &lat, &lon) != NEAR_VALID) continue;   // a is inside [0, n_asg) here
     if (PASS == 0) {
-      if (q.best_date[a] < d) atomicMax((long long*)&q.best_date[a], (long long)d);
-    } else if (q.best_date[a] == d) {
-      const int64_t s = ring_seq(q.ring, r);
-      if (q.best_seq[a] < s) atomicMax((long long*)&q.best_seq[a], (long long)s);
+      if (p.best_date[a] < d) atomicMax((long long*)&p.best_date[a], (long long)d);
+    } else if (p.best_date[a] == d) {
+      const int64_t s = ring_seq(p.ring, r);
+      if (p.best_seq[a] < s) atomicMax((long long*)&p.best_seq[a], (long long)s);
     }
   }
 }
@@ -2021,27 +2041,22 @@ __global__ __launch_bounds__(BLK) void k_near_filter(const SwNearQuery q, uint32
                                                      uint32_t* __restrict__ counters) {
   const double p1 = q.lat * (3.141592653589793 / 180.0), cos_p1 = cos(p1);
   const bool wraps = q.lon_lo > q.lon_hi;
-  uint32_t n_cand = 0, n_bad = 0;
-  ring_compact<true>(q.ring.n_rows, out_rows, out_dist, cap, &counters[0], [&](int64_t r, double* dist) {
+  PositionCounts n_pos;
+  ring_compact<true>(q.pos.ring.n_rows, out_rows, out_dist, cap, &counters[0], [&](int64_t r, double* dist) {
     int32_t a = 0;
     int64_t d = 0;
     double lat = 0.0, lon = 0.0;
-    const int cls = near_candidate(q, r, &a, &d, &lat, &lon);
+    const int cls = near_candidate(q.pos, r, &a, &d, &lat, &lon);
     bool hit = false;
-    if (cls == NEAR_VALID && (!q.latest || (q.best_date[a] == d && q.best_seq[a] == ring_seq(q.ring, r))) &&
-        lat >= q.lat_lo && lat <= q.lat_hi &&
+    if (position_looked(q.pos, cls, r, a, d) && lat >= q.lat_lo && lat <= q.lat_hi &&
         (wraps ? (lon >= q.lon_lo || lon <= q.lon_hi) : (lon >= q.lon_lo && lon <= q.lon_hi))) {
       *dist = near_haversine(p1, cos_p1, q.lon, lat, lon);
       hit = *dist <= q.radius_m;
     }
-    n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
-    n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
+    n_pos.count(cls);
     return hit;
   });
-  if (lane_id() == 0) {
-    if (n_cand) atomicAdd(&counters[1], n_cand);
-    if (n_bad) atomicAdd(&counters[2], n_bad);
-  }
+  n_pos.flush(counters, 1);
 }
 
 // ============================================================================ hot-store zone
@@ -2096,22 +2111,21 @@ __global__ __launch_bounds__(BLK) void k_zone_filter(const SwZoneQuery q, uint32
   for (int i = threadIdx.x; i < n_vtx; i += BLK) zone_vt[i] = make_double2(q.vtx[2 * i], q.vtx[2 * i + 1]);
   if (threadIdx.x == 0) zl.n[0] = zl.n[1] = 0;          // ring_compact's first barrier stands behind both
   const bool outside = q.outside != 0;
-  uint32_t n_cand = 0, n_bad = 0;
+  PositionCounts n_pos;
   int par = 0;                                          // the round's word of zl.n
   ring_compact<false>(
-      q.ring.n_rows, out_rows, nullptr, cap, &counters[0],
+      q.pos.ring.n_rows, out_rows, nullptr, cap, &counters[0],
       [&](int64_t r, double*) {
         int32_t a = 0;
         int64_t d = 0;
         double lat = 0.0, lon = 0.0;
-        const int cls = near_candidate(q, r, &a, &d, &lat, &lon);
+        const int cls = near_candidate(q.pos, r, &a, &d, &lat, &lon);
         bool hit = false, listed = false;
-        if (cls == NEAR_VALID && (!q.latest || (q.best_date[a] == d && q.best_seq[a] == ring_seq(q.ring, r)))) {
+        if (position_looked(q.pos, cls, r, a, d)) {
           listed = lat >= q.lat_lo && lat <= q.lat_hi && lon >= q.lon_lo && lon <= q.lon_hi;
           hit = !listed && outside;
         }
-        n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
-        n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
+        n_pos.count(cls);
         const ull mask = __ballot(listed);
         if (mask) {
           uint32_t base = 0;
@@ -2132,16 +2146,13 @@ __global__ __launch_bounds__(BLK) void k_zone_filter(const SwZoneQuery q, uint32
           bool hit = false;
           if (i < n) {
             row = zl.rows[i];
-            hit = zone_inside(zone_vt, n_vtx, q.v0[row], q.v1[row]) != outside;
+            hit = zone_inside(zone_vt, n_vtx, q.pos.v0[row], q.pos.v1[row]) != outside;
           }
           push(hit, row, 0.0);
         }
         par ^= 1;
       });
-  if (lane_id() == 0) {
-    if (n_cand) atomicAdd(&counters[1], n_cand);
-    if (n_bad) atomicAdd(&counters[2], n_bad);
-  }
+  n_pos.flush(counters, 1);
 }
 
 // ============================================================================ hot-store grid
@@ -2201,20 +2212,20 @@ __global__ __launch_bounds__(BLK) void k_grid_count(const SwGridQuery q, SwGridC
     }
     __syncthreads();
   }
-  uint32_t n_cand = 0, n_bad = 0, n_out = 0;
+  PositionCounts n_pos;
+  uint32_t n_out = 0;
   const int64_t stride = (int64_t)gridDim.x * BLK;
   // whole waves take every turn (the ballots count them); a row past the ring is no candidate
-  for (int64_t r0 = (int64_t)BID * BLK; r0 < q.ring.n_rows; r0 += stride) {
+  for (int64_t r0 = (int64_t)BID * BLK; r0 < q.pos.ring.n_rows; r0 += stride) {
     const int64_t r = r0 + threadIdx.x;
     int32_t a = 0;
     int64_t d = 0;
     double lat = 0.0, lon = 0.0;
-    const int cls = near_candidate(q, r, &a, &d, &lat, &lon);
-    const bool looked = cls == NEAR_VALID && (!q.latest || (q.best_date[a] == d && q.best_seq[a] == ring_seq(q.ring, r)));
+    const int cls = near_candidate(q.pos, r, &a, &d, &lat, &lon);
+    const bool looked = position_looked(q.pos, cls, r, a, d);
     uint32_t cell = 0;
     const bool in = looked && grid_cell(q, lat, lon, &cell);
-    n_cand += (uint32_t)__popcll(__ballot(cls != NEAR_NO));
-    n_bad += (uint32_t)__popcll(__ballot(cls == NEAR_INVALID));
+    n_pos.count(cls);
     n_out += (uint32_t)__popcll(__ballot(looked && !in));
     if (in) {
       if constexpr (LDS) {
@@ -2235,11 +2246,8 @@ __global__ __launch_bounds__(BLK) void k_grid_count(const SwGridQuery q, SwGridC
       grid_date(cells, c, l_date[c]);
     }
   }
-  if (lane_id() == 0) {
-    if (n_cand) atomicAdd(&counters[0], n_cand);
-    if (n_bad) atomicAdd(&counters[1], n_bad);
-    if (n_out) atomicAdd(&counters[2], n_out);
-  }
+  n_pos.flush(counters, 0);
+  if (lane_id() == 0 && n_out) atomicAdd(&counters[2], n_out);
 }
 
 // ============================================================================ hot-store ranking
@@ -2305,11 +2313,14 @@ __device__ __forceinline__ void rank_fold_global(int64_t* __restrict__ tab, int6
 }
 
 // counters: [0] candidates, [1] NaN measurements, [2] ungrouped rows ([3]: k_rank_emit's groups).
-// LDS: 28 B of dynamic LDS per key, the three int64 arrays first.  COMBINE (global form only): runs of
-// equal keys in a wave are reduced across lanes and only their heads issue atomics.
+// LDS: 28 B of dynamic LDS per key, the three int64 arrays first.  COMBINE, the global form: runs of
+// equal keys in a wave are reduced across lanes and only their heads issue atomics (row by row it took
+// three times as long, profiles/hot_rank/README.md).  COMBINE is always !LDS now: the second parameter
+// is redundant and stays only so that the two kernels keep the names profiles/ and docs/ cite.
 template <bool LDS, bool COMBINE>
 __global__ __launch_bounds__(BLK) void k_rank_fold(const SwRankQuery q, int64_t* __restrict__ tab,
                                                    uint32_t* __restrict__ counters) {
+  static_assert(LDS != COMBINE, "k_rank_fold<true, false> or <false, true>");
   extern __shared__ int64_t rank_tab[];
   const int64_t nk = q.n_keys;
   const bool values = q.event_type == SW_EV_MEASUREMENT;
@@ -2346,7 +2357,7 @@ __global__ __launch_bounds__(BLK) void k_rank_fold(const SwRankQuery q, int64_t*
         }
         atomicMax((long long*)&l_date[key], (long long)d);
       }
-    } else if constexpr (COMBINE) {
+    } else {
       const ull grouped = __ballot(in);
       if (!grouped) continue;                     // the whole wave
       // a grouped lane whose left neighbour is grouped with the same key belongs to that neighbour's run;
@@ -2373,8 +2384,6 @@ __global__ __launch_bounds__(BLK) void k_rank_fold(const SwRankQuery q, int64_t*
         }
       }
       if (head) rank_fold_global(tab, nk, key, n, values, lo, hi, dd);
-    } else {
-      if (in) rank_fold_global(tab, nk, key, 1u, values, vk, vk, d);
     }
   }
   if constexpr (LDS) {
@@ -2942,47 +2951,53 @@ int sw_store_series(const SwSeriesQuery* q, const uint32_t* sums, const uint32_t
   return (int)hipGetLastError();
 }
 
+// What the queries that read whole ring rows by position ask of a view before any launch: an ordered
+// date range, 1 .. 2^32 rows (a match is a uint32 row), a bitmap and the oldest row inside the ring.
+static bool ring_view_ok(const SwRingView& v) {
+  return v.start <= v.end && v.n_rows >= 1 && v.n_rows <= ((int64_t)1 << 32) && v.n_asg >= 1 && v.head >= 0 &&
+         v.head < v.n_rows;
+}
+
+// The front of the three location queries: refuses a bad view (with `latest`, one without its tables)
+// before anything is launched, zeroes n counter words and, with `latest`, runs the two best passes.
+static int position_begin(const SwPositionView& p, uint32_t* counters, int n, hipStream_t s) {
+  if (!ring_view_ok(p.ring) || (p.latest && (!p.best_date || !p.best_seq))) return (int)hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(counters, 0, n * sizeof(uint32_t), s);
+  if (e != hipSuccess) return (int)e;
+  if (p.latest) {
+    k_near_best<0><<<grid_for(p.ring.n_rows), BLK, 0, s>>>(p);
+    k_near_best<1><<<grid_for(p.ring.n_rows), BLK, 0, s>>>(p);
+  }
+  return 0;
+}
+
 // Locations near a point: matches of *q as (ring row, distance) into out_rows / out_dist [cap], unordered;
 // counters (u32[3], zeroed here): matches (the total even past cap), candidates, invalid candidates.
-// q->latest: best_date / best_seq [n_asg] hold INT64_MIN on entry.  The query is refused, before any
-// launch, unless the centre, the radius and the box are finite and in range.
+// q->pos.latest: best_date / best_seq [n_asg] hold INT64_MIN, or what these passes left there over the
+// same ring, on entry.  The query is refused, before any launch, unless the centre, the radius and the
+// box are finite and in range.
 int sw_store_near(const SwNearQuery* q, uint32_t* out_rows, double* out_dist, int64_t cap, uint32_t* counters,
                   hipStream_t s) {
   const bool centre = fabs(q->lat) <= 90.0 && fabs(q->lon) <= 180.0 && q->radius_m >= 0.0 && q->radius_m <= 1.0e7;
   const bool box = q->lat_lo <= q->lat_hi && fabs(q->lon_lo) <= 180.0 && fabs(q->lon_hi) <= 180.0;
-  const SwRingView& v = q->ring;
-  if (!centre || !box || v.start > v.end || v.n_rows < 1 || v.n_rows > ((int64_t)1 << 32) || v.n_asg < 1 || cap < 1 ||
-      v.head < 0 || v.head >= v.n_rows || (q->latest && (!q->best_date || !q->best_seq)))
-    return (int)hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(counters, 0, 3 * sizeof(uint32_t), s);
-  if (e != hipSuccess) return (int)e;
-  if (q->latest) {
-    k_near_best<0><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
-    k_near_best<1><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
-  }
-  k_near_filter<<<grid_for((v.n_rows + STAGE_U - 1) / STAGE_U), BLK, 0, s>>>(*q, out_rows, out_dist, cap, counters);
+  if (!centre || !box || cap < 1) return (int)hipErrorInvalidValue;
+  if (const int rc = position_begin(q->pos, counters, 3, s)) return rc;
+  const int64_t n = q->pos.ring.n_rows;
+  k_near_filter<<<grid_for((n + STAGE_U - 1) / STAGE_U), BLK, 0, s>>>(*q, out_rows, out_dist, cap, counters);
   return (int)hipGetLastError();
 }
 
 // Locations in a zone: matches of *q as ring rows into out_rows [cap], unordered; counters (u32[3],
-// zeroed here) as sw_store_near's.  q->latest: best_date / best_seq [n_asg] hold INT64_MIN on entry.
-// The query is refused, before any launch, unless the vertex count is in range, the table is there and
-// the box is finite and ordered.
+// zeroed here) and the `latest` tables as sw_store_near's.  The query is refused, before any launch,
+// unless the vertex count is in range, the table is there and the box is finite and ordered.
 int sw_store_zone(const SwZoneQuery* q, uint32_t* out_rows, int64_t cap, uint32_t* counters, hipStream_t s) {
   const bool poly = q->n_vtx >= 3 && q->n_vtx <= SW_ZONE_MAX_VTX && q->vtx;
   const bool box = fabs(q->lat_lo) <= 90.0 && fabs(q->lat_hi) <= 90.0 && fabs(q->lon_lo) <= 180.0 &&
                    fabs(q->lon_hi) <= 180.0 && q->lat_lo <= q->lat_hi && q->lon_lo <= q->lon_hi;
-  const SwRingView& v = q->ring;
-  if (!poly || !box || v.start > v.end || v.n_rows < 1 || v.n_rows > ((int64_t)1 << 32) || v.n_asg < 1 || cap < 1 ||
-      v.head < 0 || v.head >= v.n_rows || (q->latest && (!q->best_date || !q->best_seq)))
-    return (int)hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(counters, 0, 3 * sizeof(uint32_t), s);
-  if (e != hipSuccess) return (int)e;
-  if (q->latest) {
-    k_near_best<0><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
-    k_near_best<1><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
-  }
-  k_zone_filter<<<grid_for((v.n_rows + STAGE_U - 1) / STAGE_U), BLK, (size_t)q->n_vtx * sizeof(double2), s>>>(
+  if (!poly || !box || cap < 1) return (int)hipErrorInvalidValue;
+  if (const int rc = position_begin(q->pos, counters, 3, s)) return rc;
+  const int64_t n = q->pos.ring.n_rows;
+  k_zone_filter<<<grid_for((n + STAGE_U - 1) / STAGE_U), BLK, (size_t)q->n_vtx * sizeof(double2), s>>>(
       *q, out_rows, cap, counters);
   return (int)hipGetLastError();
 }
@@ -2998,28 +3013,20 @@ int64_t sw_grid_lds_cells(int64_t cells) {
 
 // Location density grid: cells [q->n_rows * q->n_cols], row-major, zeroed here (an empty cell's date is
 // left at INT64_MIN); counters (u32[3], zeroed here): candidates, invalid candidates, valid looked-at
-// rows outside the box.  q->latest: best_date / best_seq [n_asg] hold INT64_MIN on entry.  The query is
-// refused, before any launch, unless the box is finite, in range and ordered as `crossing` says, the
-// grid within SW_GRID_MAX_CELLS and the steps positive: what keeps a cell inside the table.
+// rows outside the box; the `latest` tables as sw_store_near's.  The query is refused, before any
+// launch, unless the box is finite, in range and ordered as `crossing` says, the grid within
+// SW_GRID_MAX_CELLS and the steps positive: what keeps a cell inside the table.
 int sw_store_grid(const SwGridQuery* q, SwGridCell* cells, uint32_t* counters, hipStream_t s) {
   const bool box = q->lat_lo >= -90.0 && q->lat_lo < q->lat_hi && q->lat_hi <= 90.0 && fabs(q->lon_lo) <= 180.0 &&
                    fabs(q->lon_hi) <= 180.0 && q->lon_lo != q->lon_hi && (q->crossing != 0) == (q->lon_lo > q->lon_hi);
   const bool grid = q->n_rows >= 1 && q->n_cols >= 1 && q->n_rows <= SW_GRID_MAX_CELLS &&
                     q->n_cols <= SW_GRID_MAX_CELLS && q->n_rows * q->n_cols <= SW_GRID_MAX_CELLS && q->d_lat > 0.0 &&
                     q->d_lon > 0.0 && q->d_lat <= 180.0 && q->d_lon <= 360.0;
-  const SwRingView& v = q->ring;
-  if (!box || !grid || !cells || v.start > v.end || v.n_rows < 1 || v.n_rows > ((int64_t)1 << 32) || v.n_asg < 1 ||
-      v.head < 0 || v.head >= v.n_rows || (q->latest && (!q->best_date || !q->best_seq)))
-    return (int)hipErrorInvalidValue;
+  if (!box || !grid || !cells) return (int)hipErrorInvalidValue;
+  if (const int rc = position_begin(q->pos, counters, 3, s)) return rc;
   const int64_t n_cells = q->n_rows * q->n_cols;
-  hipError_t e = hipMemsetAsync(counters, 0, 3 * sizeof(uint32_t), s);
-  if (e != hipSuccess) return (int)e;
   k_grid_init<<<(unsigned)((n_cells + BLK - 1) / BLK), BLK, 0, s>>>(cells, n_cells);
-  if (q->latest) {
-    k_near_best<0><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
-    k_near_best<1><<<grid_for(v.n_rows), BLK, 0, s>>>(*q);
-  }
-  const int g = grid_for((v.n_rows + STAGE_U - 1) / STAGE_U);
+  const int g = grid_for((q->pos.ring.n_rows + STAGE_U - 1) / STAGE_U);
   if (n_cells <= grid_lds_cells)
     k_grid_count<true><<<g, BLK, (size_t)n_cells * 12, s>>>(*q, cells, counters);
   else
@@ -3036,14 +3043,6 @@ int64_t sw_rank_lds_keys(int64_t keys) {
   return rank_lds_keys;
 }
 
-// Whether the global form reduces a wave's runs of equal keys before its atomics (1, the default) or
-// issues them row by row (0): what profiles/hot_rank measures against.  on < 0: no change.
-static int rank_combine = 1;
-int sw_rank_combine(int on) {
-  if (on >= 0) rank_combine = on != 0;
-  return rank_combine;
-}
-
 // Ranking: tab (int64 [SW_RANK_TAB_WORDS * n_keys]) is set up here; cells and sort_key [n_keys] receive the
 // non-empty groups in any order; counters (u32[4], zeroed here): candidates, NaN measurements,
 // ungrouped rows, groups.  The query is refused, before any launch, unless the event type is one of the
@@ -3058,8 +3057,7 @@ int sw_store_rank(const SwRankQuery* q, int64_t* tab, SwRankCell* cells, int64_t
                     (q->stat >= SW_RANK_MIN && q->stat <= SW_RANK_LAST && q->event_type == SW_EV_MEASUREMENT && q->name_on);
   if (!type || !stat || q->n_keys < 0 || q->n_keys > SW_RANK_MAX_KEYS || q->min_level < -1 || q->min_level > 3 ||
       (q->min_level >= 0 && q->event_type != SW_EV_ALERT) || !q->level || !q->name || !q->v0 || !q->key || !counters ||
-      (q->n_keys && (!tab || !cells || !sort_key)) || v.start > v.end || v.n_rows < 1 ||
-      v.n_rows > ((int64_t)1 << 32) || v.n_asg < 1 || v.head < 0 || v.head >= v.n_rows)
+      (q->n_keys && (!tab || !cells || !sort_key)) || !ring_view_ok(v))
     return (int)hipErrorInvalidValue;
   const int64_t nk = q->n_keys;
   hipError_t e = hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), s);
@@ -3069,10 +3067,8 @@ int sw_store_rank(const SwRankQuery* q, int64_t* tab, SwRankCell* cells, int64_t
   const int g = grid_for((v.n_rows + STAGE_U - 1) / STAGE_U);
   if (nk <= rank_lds_keys)
     k_rank_fold<true, false><<<g, BLK, (size_t)nk * 28, s>>>(*q, tab, counters);
-  else if (rank_combine)
-    k_rank_fold<false, true><<<g, BLK, 0, s>>>(*q, tab, counters);
   else
-    k_rank_fold<false, false><<<g, BLK, 0, s>>>(*q, tab, counters);
+    k_rank_fold<false, true><<<g, BLK, 0, s>>>(*q, tab, counters);
   if (nk) {
     k_rank_last<<<grid_for(v.n_rows), BLK, 0, s>>>(*q, tab);
     k_rank_emit<<<gk, BLK, 0, s>>>(*q, tab, cells, sort_key, counters);
@@ -3214,6 +3210,7 @@ int sw_abi_sizes(int64_t* out) {
   out[14] = sizeof(SwZoneQuery);
   out[15] = sizeof(SwGridQuery);
   out[16] = sizeof(SwRankQuery);
+  out[17] = sizeof(SwPositionView);
   return 0;
 }
 

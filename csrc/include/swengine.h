@@ -318,18 +318,26 @@ typedef struct SwSeriesQuery {
 } SwSeriesQuery;
 static_assert(sizeof(SwSeriesQuery) == 144, "SwSeriesQuery is 18 8-byte words");
 
+// A location row as the three location queries below see it: the ring view plus the latitude and longitude
+// columns, and `latest` with its two tables (near_candidate, k_near_best and position_looked in
+// csrc/hip/swgpu.hip).  POSITION_QUERY names the words; the three queries begin with it and add their own.
+typedef struct SwPositionView {
+  SwRingView ring;             // ring.n_asg is also the entries of the two tables below
+  const double* v0;            // ring columns: latitude
+  const double* v1;            // longitude
+  int64_t latest;              // 1: look at a row only if it is its assignment's newest valid candidate
+  int64_t* best_date;          // [n_asg] latest only: date of that row, then its store sequence
+  int64_t* best_seq;
+} SwPositionView;
+static_assert(sizeof(SwPositionView) == 120, "SwPositionView is 15 8-byte words");
+
 // A locations-near query (sw_store_near; NEAR_QUERY names the words, the doubles written by their
 // bits).  The box is the host's conservative cover of the cap (pipeline/near.py: near_box), in
 // degrees; lon_lo > lon_hi: the longitude interval wraps across +-180.
 typedef struct SwNearQuery {
-  SwRingView ring;             // ring.n_asg is also the entries of the two tables below
-  const double* v0;            // ring columns: latitude
-  const double* v1;            // longitude
+  SwPositionView pos;
   double lat, lon, radius_m;   // centre (degrees) and radius
   double lat_lo, lat_hi, lon_lo, lon_hi;
-  int64_t latest;              // 1: keep a row only if it is its assignment's newest valid candidate
-  int64_t* best_date;          // [n_asg] latest only: date of that row, then its store sequence
-  int64_t* best_seq;
 } SwNearQuery;
 static_assert(sizeof(SwNearQuery) == 176, "SwNearQuery is 22 8-byte words");
 
@@ -337,16 +345,11 @@ static_assert(sizeof(SwNearQuery) == 176, "SwNearQuery is 22 8-byte words");
 // bits).  The polygon is planar in (lat, lon), its ring implicitly closed; the box is the host's cover
 // of it (pipeline/zone.py: zone_box), edges included: a point outside the box is outside the polygon.
 typedef struct SwZoneQuery {
-  SwRingView ring;             // ring.n_asg is also the entries of the two tables below
-  const double* v0;            // ring columns: latitude
-  const double* v1;            // longitude
+  SwPositionView pos;
   const double* vtx;           // [2 * n_vtx] vertices as (lat, lon) pairs
   int64_t n_vtx;               // 3 .. SW_ZONE_MAX_VTX
   double lat_lo, lat_hi, lon_lo, lon_hi;
   int64_t outside;             // 1: a valid candidate matches when it is not inside
-  int64_t latest;              // 1: keep a row only if it is its assignment's newest valid candidate
-  int64_t* best_date;          // [n_asg] latest only: date of that row, then its store sequence
-  int64_t* best_seq;
 } SwZoneQuery;
 static_assert(sizeof(SwZoneQuery) == 176, "SwZoneQuery is 22 8-byte words");
 
@@ -365,16 +368,11 @@ static_assert(sizeof(SwGridCell) == 16, "SwGridCell is two 8-byte words");
 // d_lat / d_lon are the host's cell steps (pipeline/grid.py: grid_steps): the cell formula divides by
 // them as they stand, so every engine puts a row in the same cell.
 typedef struct SwGridQuery {
-  SwRingView ring;             // ring.n_asg is also the entries of the two tables below
-  const double* v0;            // ring columns: latitude
-  const double* v1;            // longitude
+  SwPositionView pos;
   double lat_lo, lat_hi, lon_lo, lon_hi;
   double d_lat, d_lon;         // a cell's height and width in degrees
   int64_t n_rows, n_cols;      // the grid; row 0 is the south edge, column 0 the lon_lo one
   int64_t crossing;
-  int64_t latest;              // 1: count a row only if it is its assignment's newest valid candidate
-  int64_t* best_date;          // [n_asg] latest only: date of that row, then its store sequence
-  int64_t* best_seq;
 } SwGridQuery;
 static_assert(sizeof(SwGridQuery) == 192, "SwGridQuery is 24 8-byte words");
 

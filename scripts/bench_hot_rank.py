@@ -13,10 +13,8 @@ runs as long as a wave.  Then times, per call:
 (a) and (b) alternate within a repetition; ``--paged-reps`` bounds how many repetitions also run (b).
 Before any time is taken (a) is checked against (b): the cells' bytes and the counters equal.
 
-``--forms`` adds what ``SW_RANK_LDS_KEYS`` and run combining rest on, (a) alone, alternated within a
-repetition: the LDS form against the global form (limit 0) grouping by a few-key dimension and by the hot
-device's customer, and the global form with and without run combining at the fleet shape (every
-assignment, 1.1M keys) and at the hot-key shape (the hot device alone).
+``--forms`` adds what ``SW_RANK_LDS_KEYS`` rests on, (a) alone, alternated within a repetition: the LDS
+form against the global form (limit 0) grouping by a few-key dimension and by the hot device's customer.
 
     python scripts/bench_hot_rank.py --store 134217728 --forms
 """
@@ -42,7 +40,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--paged-reps", type=int, default=2, help="repetitions that also run (b)")
     ap.add_argument("--gpu-only", action="store_true", help="time (a) alone (for a profiler run)")
-    ap.add_argument("--forms", action="store_true", help="compare the fold's forms and run combining")
+    ap.add_argument("--forms", action="store_true", help="compare the fold's LDS and global forms")
     args = ap.parse_args()
     import torch
 
@@ -121,7 +119,7 @@ def main():
 
     out = {"store_events": int(min(g.cursor, args.store)), "fill_s": round(fill_s, 1), "reps": args.reps,
            "paged_reps": 0 if args.gpu_only else args.paged_reps, "lds_keys_compiled": compiled,
-           "key_spaces": {grp: g.rank_key_space(grp)[1] for grp in col}, "queries": {}, "forms": {}, "combine": {}}
+           "key_spaces": {grp: g.rank_key_space(grp)[1] for grp in col}, "queries": {}, "forms": {}}
     for qname, q in queries.items():
         first = g.rank_store(**q)                                     # warm (buffers, code objects)
         can_page = not args.gpu_only and q["event_type"] != M
@@ -171,17 +169,6 @@ def main():
             res, info = alternate(q, [compiled, 0], lambda lim: lib.sw_rank_lds_keys(lim))
             lib.sw_rank_lds_keys(compiled)
             out["forms"][sname] = {"rows": info["rows"], "groups": info["groups"], "lds": res[str(compiled)], "global": res["0"]}
-        shapes = {
-            "fleet: count by assignment": dict(event_type=M, group="assignment", k=10),
-            "fleet: max of one name by assignment": dict(event_type=M, group="assignment", stat="max", k=10, name_hash=name),
-            "hot key: the hot device by assignment": dict(event_type=M, group="assignment", stat="max", k=10, asg_idx=[0],
-                                                          name_hash=name),
-            "hot key: the hot device, every name": dict(event_type=M, group="assignment", k=10, asg_idx=[0]),
-        }
-        for sname, q in shapes.items():
-            res, info = alternate(q, [1, 0], lambda on: lib.sw_rank_combine(on))
-            lib.sw_rank_combine(1)
-            out["combine"][sname] = {"rows": info["rows"], "groups": info["groups"], "combined": res["1"], "row_by_row": res["0"]}
     print(json.dumps(out))
 
 

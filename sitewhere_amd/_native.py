@@ -318,7 +318,6 @@ def gpu():
         _proto(lib, "sw_grid_lds_cells", c_int64, c_int64)
         _proto(lib, "sw_store_rank", c_int32, P, P, P, P, P, P)
         _proto(lib, "sw_rank_lds_keys", c_int64, c_int64)
-        _proto(lib, "sw_rank_combine", c_int32, c_int32)
         _proto(lib, "sw_scan_u32", c_int32, P, c_int64, P, P, P, c_int64, P)
         _proto(lib, "sw_state_lookup", c_int32, P, c_int64, c_int32, c_int32, P, P, P)
         _proto(lib, "sw_abi_sizes", c_int32, P)

@@ -139,26 +139,28 @@ SERIES_MAX_CELLS = 65536       # SW_SERIES_MAX_CELLS
 RING_QUERY = ("etype", "asg", "date", "n_rows", "seq0", "head", "bits", "n_asg", "start", "end")
 # The int64 words of a series query (SwSeriesQuery in swengine.h), in order.
 SERIES_QUERY = RING_QUERY + ("name", "v0", "names", "n_names", "bucket_ms", "n_buckets", "rounds", "grid")
-# The 8-byte words of a locations-near query (SwNearQuery in swengine.h), in order; NEAR_QUERY_F64 are
-# the doubles among them (written by their bits).
-NEAR_QUERY = RING_QUERY + ("v0", "v1", "lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "latest",
-                           "best_date", "best_seq")
+# The 8-byte words of the position view the three location queries begin with (SwPositionView in
+# swengine.h), in order: the ring view, the latitude and longitude columns, `latest` and its two tables.
+POSITION_QUERY = RING_QUERY + ("v0", "v1", "latest", "best_date", "best_seq")
+# The 8-byte words of a locations-near query (SwNearQuery in swengine.h), in order: the position view,
+# then NEAR_WORDS, the query's own; NEAR_QUERY_F64 are the doubles among them (written by their bits).
+NEAR_WORDS = ("lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi")
+NEAR_QUERY = POSITION_QUERY + NEAR_WORDS
 NEAR_QUERY_F64 = ("lat", "lon", "radius_m", "lat_lo", "lat_hi", "lon_lo", "lon_hi")
 # The 8-byte words of a locations-in-zone query (SwZoneQuery in swengine.h), in order; ZONE_QUERY_F64 are
 # the doubles among them.
-ZONE_QUERY = RING_QUERY + ("v0", "v1", "vtx", "n_vtx", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "outside", "latest",
-                           "best_date", "best_seq")
+ZONE_WORDS = ("vtx", "n_vtx", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "outside")
+ZONE_QUERY = POSITION_QUERY + ZONE_WORDS
 ZONE_QUERY_F64 = ("lat_lo", "lat_hi", "lon_lo", "lon_hi")
 # One cell of a location density grid (SwGridCell in swengine.h): the locations in it and the newest of
 # their dates; an empty cell is all zero bytes.
 GRID_CELL = np.dtype([("count", "<i8"), ("last_date", "<i8")])
 assert GRID_CELL.itemsize == 16
 # The 8-byte words of a density-grid query (SwGridQuery in swengine.h), in order; GRID_QUERY_F64 are the
-# doubles among them.  GRID_WORDS are the query's own: its n_rows (the grid's rows) shares its name with the
-# ring view's (the ring's rows), so the two parts are filled in separately.
-GRID_WORDS = ("v0", "v1", "lat_lo", "lat_hi", "lon_lo", "lon_hi", "d_lat", "d_lon", "n_rows", "n_cols", "crossing",
-              "latest", "best_date", "best_seq")
-GRID_QUERY = RING_QUERY + GRID_WORDS
+# doubles among them.  Its n_rows (the grid's rows) shares its name with the ring view's (the ring's rows):
+# a query's own words are filled in apart from the view's.
+GRID_WORDS = ("lat_lo", "lat_hi", "lon_lo", "lon_hi", "d_lat", "d_lon", "n_rows", "n_cols", "crossing")
+GRID_QUERY = POSITION_QUERY + GRID_WORDS
 GRID_QUERY_F64 = ("lat_lo", "lat_hi", "lon_lo", "lon_hi", "d_lat", "d_lon")
 # One group of a ranking over the ring (SwRankCell in swengine.h): its key, its rows, min / max / last of
 # their v0 (0.0 for a type that has no value) and the (date, event id) of its newest row.

@@ -82,10 +82,10 @@ class SwEngineArgs(ctypes.Structure):
 
 
 def abi_sizes(lib) -> dict:
-    buf = (ctypes.c_int64 * 17)()
+    buf = (ctypes.c_int64 * 18)()
     lib.sw_abi_sizes(ctypes.cast(buf, ctypes.c_void_p))
     return {"event_rec": buf[0], "out_rec": buf[1], "engine_args": buf[2], "name_ref": buf[3], "zone_test": buf[4],
             "reg_slot": buf[5], "asg_state": buf[6], "ms_slot": buf[7], "wire_rec": buf[8],
             "str_ref": buf[9], "step_snapshot": buf[10], "near_query": buf[11], "ring_view": buf[12],
             "series_query": buf[13], "zone_query": buf[14], "grid_query": buf[15],
-            "rank_query": buf[16]}
+            "rank_query": buf[16], "position_view": buf[17]}

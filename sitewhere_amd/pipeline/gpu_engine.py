@@ -23,10 +23,10 @@ import numpy as np
 import torch
 
 from .._native import gpu_gil as gpu_lib
-from ..models.columnar import (EVENT_REC, RANK_CELL, RANK_QUERY, GRID_CELL, GRID_QUERY_F64, GRID_WORDS, N_STATS, NEAR_QUERY, NEAR_QUERY_F64,
-                               OUT_REC, NAME_REF, OUT_REC_SIZE, RING_QUERY, SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK, SC_N_OUT,
+from ..models.columnar import (EVENT_REC, RANK_CELL, RANK_QUERY, GRID_CELL, GRID_QUERY_F64, GRID_WORDS, N_STATS, NEAR_QUERY_F64, NEAR_WORDS,
+                               OUT_REC, NAME_REF, OUT_REC_SIZE, POSITION_QUERY, RING_QUERY, SC_N_GEN, SC_N_NEW_NAMES, SC_N_OK, SC_N_OUT,
                                SC_N_RECS, SC_N_REJ, SC_N_RULE, SC_N_WORK, SC_NAMES, SC_OVERFLOW, SEG_ST_BYTES, SEG_ST_FIRST, SEG_ST_WORDS, SERIES_CELL, SERIES_QUERY,
-                               ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC, ZONE_QUERY, ZONE_QUERY_F64)
+                               ST_RECHECK, STEP_SNAPSHOT, STR_REF, WIRE_REC, ZONE_QUERY_F64, ZONE_WORDS)
 from ..ops.engine_abi import SwEngineArgs
 from .config import EngineConfig
 from .bus_io import host_view
@@ -1326,6 +1326,47 @@ class GpuInboundEngine(EngineBase):
             b = bufs[key] = torch.empty(n, dtype=dtype, device=self.device)
         return b
 
+    @staticmethod
+    def _counters(counters, n: int):
+        """The first ``n`` words of a query's device counters, read back (this waits for the query's kernels)."""
+        return (int(x) for x in counters[:n].cpu().numpy().view(np.uint32))
+
+    def _position_view(self, pool: str, asg_idx, start, end, latest: bool):
+        """What the three location queries start from, read under the engine lock: (cursor, ring rows,
+        ``POSITION_QUERY``'s words or None for an empty ring, where nothing is allocated or launched, the
+        bitmap tensor they point into -- the caller holds it so that it outlives the launch --, the answer's
+        ``hot_since``).  ``latest``: ``pool``'s ``best`` table is filled with INT64_MIN here, once: a
+        repeated pass finds its own maxima there and reaches them again."""
+        cur, view, bits = self._ring_view(asg_idx, start, end)
+        n, nbits, best = view["n_rows"], view["n_asg"], 0
+        if n == 0:
+            return cur, 0, None, bits, None
+        if latest:
+            tab = self._ring_buf(pool, "best", 2 * nbits, torch.int64)
+            tab[:2 * nbits].fill_(_I64.min)
+            best = _ptr(tab)
+        head = self._query_words(POSITION_QUERY, (), dict(
+            view, v0=_ptr(self.store["v0"]), v1=_ptr(self.store["v1"]), latest=int(latest), best_date=best,
+            best_seq=best + 8 * nbits if latest else 0))
+        return cur, n, head, bits, self._hot_since(cur)
+
+    def _empty_page(self):
+        """The page of a row query over an empty ring, (columns, event ids): host arrays, no launch."""
+        cols = {k: torch.empty(0, dtype=v.dtype).numpy() for k, v in self.store.items()}
+        return self._u64_cols(cols), np.zeros(0, np.int64)
+
+    def _grow_and_repeat(self, pool: str, rows0: int, n: int, launch):
+        """A row query's (match count, match buffers...): ``launch(cap)`` runs it into match buffers of ``cap``
+        rows and returns just that.  They start at ``rows0`` rows (or what an earlier query grew ``pool``'s
+        to; at most the ring's ``n``); when that is short they grow to the match count and the pass is repeated."""
+        held = self._ring_bufs.get(pool, {}).get("rows")
+        cap = min(n, max(rows0, 0 if held is None else held.numel()))
+        while True:
+            out = launch(cap)
+            if out[0] <= cap:
+                return out
+            cap = out[0]
+
     def _order_page(self, rows, cur, page_number, page_size, dist=None, by_distance=False):
         """Order a match set (ring rows, int64, on the device; ``dist`` beside them) and fetch one page:
         (columns, event ids, distances or None).  Stable sorts, least significant key first: event id
@@ -1425,40 +1466,24 @@ class GpuInboundEngine(EngineBase):
 
     def _near_store(self, lat, lon, radius_m, asg_idx, start, end, latest, order, page_number, page_size):
         from .near import near_box
-        st = self.store
-        info = {"candidates": 0, "invalid": 0, "hot_since": None}
-        cur, view, bits = self._ring_view(asg_idx, start, end)
-        n, nbits = view["n_rows"], view["n_asg"]
-        if n == 0:
-            cols = {k: torch.empty(0, dtype=v.dtype).numpy() for k, v in st.items()}       # host tensors: no launch
-            return 0, self._u64_cols(cols), np.zeros(0, np.int64), np.zeros(0, np.float64), info
-        info["hot_since"] = self._hot_since(cur)
+        cur, n, head, bits, hot_since = self._position_view("near", asg_idx, start, end, latest)
+        info = {"candidates": 0, "invalid": 0, "hot_since": hot_since}
+        if head is None:
+            return (0, *self._empty_page(), np.zeros(0, np.float64), info)
         buf = functools.partial(self._ring_buf, "near")
-        best = None
-        if latest:
-            best = buf("best", 2 * nbits, torch.int64)
-            best[:2 * nbits].fill_(_I64.min)
         lat_lo, lat_hi, lon_lo, lon_hi = near_box(lat, lon, radius_m)
-        q = self._query_words(NEAR_QUERY, NEAR_QUERY_F64, dict(
-            view, v0=_ptr(st["v0"]), v1=_ptr(st["v1"]), lat=lat, lon=lon, radius_m=radius_m, lat_lo=lat_lo, lat_hi=lat_hi,
-            lon_lo=lon_lo, lon_hi=lon_hi, latest=int(latest), best_date=_ptr(best) if latest else 0,
-            best_seq=_ptr(best) + 8 * nbits if latest else 0))
-        counters = buf("counters", 3)
-        # the match buffers start at _near_rows0 rows (or what an earlier query grew them to); when that is
-        # short they grow to the match count and the pass is repeated
-        held = self._ring_bufs["near"].get("rows")
-        cap = min(n, max(self._near_rows0, 0 if held is None else held.numel()))
-        stream = self._stream()
-        while True:
+        q = np.concatenate([head, self._query_words(NEAR_WORDS, NEAR_QUERY_F64, dict(
+            lat=lat, lon=lon, radius_m=radius_m, lat_lo=lat_lo, lat_hi=lat_hi, lon_lo=lon_lo, lon_hi=lon_hi))])
+        counters, stream = buf("counters", 3), self._stream()
+
+        def launch(cap):
             rows, dist = buf("rows", cap), buf("dist", cap, torch.float64)
             _chk(self.lib.sw_store_near(q.ctypes.data, _ptr(rows), _ptr(dist), cap, _ptr(counters), stream),
                  "sw_store_near")
-            total, info["candidates"], info["invalid"] = (int(x) for x in counters[:3].cpu().numpy().view(np.uint32))
-            if total <= cap:
-                break
-            cap = total
-            if latest:
-                best[:2 * nbits].fill_(_I64.min)
+            total, info["candidates"], info["invalid"] = self._counters(counters, 3)
+            return total, rows, dist
+
+        total, rows, dist = self._grow_and_repeat("near", self._near_rows0, n, launch)
         cols, eids, dist = self._order_page(rows[:total].long() & 0xFFFFFFFF, cur, page_number, page_size, dist[:total],
                                             order == "distance")
         return total, cols, eids, dist, info
@@ -1482,41 +1507,26 @@ class GpuInboundEngine(EngineBase):
 
     def _zone_store(self, poly, asg_idx, start, end, outside, latest, page_number, page_size):
         from .zone import zone_box
-        st = self.store
-        info = {"candidates": 0, "invalid": 0, "hot_since": None}
-        cur, view, bits = self._ring_view(asg_idx, start, end)
-        n, nbits = view["n_rows"], view["n_asg"]
-        if n == 0:
-            cols = {k: torch.empty(0, dtype=v.dtype).numpy() for k, v in st.items()}       # host tensors: no launch
-            return 0, self._u64_cols(cols), np.zeros(0, np.int64), info
-        info["hot_since"] = self._hot_since(cur)
+        cur, n, head, bits, hot_since = self._position_view("zone", asg_idx, start, end, latest)
+        info = {"candidates": 0, "invalid": 0, "hot_since": hot_since}
+        if head is None:
+            return (0, *self._empty_page(), info)
         buf = functools.partial(self._ring_buf, "zone")
-        best = None
-        if latest:
-            best = buf("best", 2 * nbits, torch.int64)
-            best[:2 * nbits].fill_(_I64.min)
         vtx = buf("vtx", 2 * len(poly), torch.float64)
         vtx[:2 * len(poly)].copy_(torch.from_numpy(poly.reshape(-1)))
         lat_lo, lat_hi, lon_lo, lon_hi = zone_box(poly)
-        q = self._query_words(ZONE_QUERY, ZONE_QUERY_F64, dict(
-            view, v0=_ptr(st["v0"]), v1=_ptr(st["v1"]), vtx=_ptr(vtx), n_vtx=len(poly), lat_lo=lat_lo, lat_hi=lat_hi,
-            lon_lo=lon_lo, lon_hi=lon_hi, outside=int(outside), latest=int(latest),
-            best_date=_ptr(best) if latest else 0, best_seq=_ptr(best) + 8 * nbits if latest else 0))
-        counters = buf("counters", 3)
-        # the match buffer starts at _zone_rows0 rows (or what an earlier query grew it to); when that is
-        # short it grows to the match count and the pass is repeated
-        held = self._ring_bufs["zone"].get("rows")
-        cap = min(n, max(self._zone_rows0, 0 if held is None else held.numel()))
-        stream = self._stream()
-        while True:
+        q = np.concatenate([head, self._query_words(ZONE_WORDS, ZONE_QUERY_F64, dict(
+            vtx=_ptr(vtx), n_vtx=len(poly), lat_lo=lat_lo, lat_hi=lat_hi, lon_lo=lon_lo, lon_hi=lon_hi,
+            outside=int(outside)))])
+        counters, stream = buf("counters", 3), self._stream()
+
+        def launch(cap):
             rows = buf("rows", cap)
             _chk(self.lib.sw_store_zone(q.ctypes.data, _ptr(rows), cap, _ptr(counters), stream), "sw_store_zone")
-            total, info["candidates"], info["invalid"] = (int(x) for x in counters[:3].cpu().numpy().view(np.uint32))
-            if total <= cap:
-                break
-            cap = total
-            if latest:
-                best[:2 * nbits].fill_(_I64.min)
+            total, info["candidates"], info["invalid"] = self._counters(counters, 3)
+            return total, rows
+
+        total, rows = self._grow_and_repeat("zone", self._zone_rows0, n, launch)
         cols, eids, _ = self._order_page(rows[:total].long() & 0xFFFFFFFF, cur, page_number, page_size)
         return total, cols, eids, info
 
@@ -1537,28 +1547,20 @@ class GpuInboundEngine(EngineBase):
 
     def _grid_store(self, box, n_rows, n_cols, asg_idx, start, end, latest):
         from .grid import grid_steps
-        st = self.store
-        info = {"candidates": 0, "invalid": 0, "outside": 0, "hot_since": None}
-        cur, view, bits = self._ring_view(asg_idx, start, end)
-        n, nbits = view["n_rows"], view["n_asg"]
-        if n == 0:
+        cur, n, head, bits, hot_since = self._position_view("grid", asg_idx, start, end, latest)
+        info = {"candidates": 0, "invalid": 0, "outside": 0, "hot_since": hot_since}
+        if head is None:
             return np.zeros((n_rows, n_cols), GRID_CELL), info                   # no launch
-        info["hot_since"] = self._hot_since(cur)
         buf = functools.partial(self._ring_buf, "grid")
-        best = None
-        if latest:
-            best = buf("best", 2 * nbits, torch.int64)
-            best[:2 * nbits].fill_(_I64.min)
         d_lat, d_lon, crossing = grid_steps(box, n_rows, n_cols)
-        q = np.concatenate([self._query_words(RING_QUERY, (), view), self._query_words(GRID_WORDS, GRID_QUERY_F64, dict(
-            v0=_ptr(st["v0"]), v1=_ptr(st["v1"]), lat_lo=box[0], lat_hi=box[1], lon_lo=box[2], lon_hi=box[3], d_lat=d_lat,
-            d_lon=d_lon, n_rows=n_rows, n_cols=n_cols, crossing=int(crossing), latest=int(latest),
-            best_date=_ptr(best) if latest else 0, best_seq=_ptr(best) + 8 * nbits if latest else 0))])
+        q = np.concatenate([head, self._query_words(GRID_WORDS, GRID_QUERY_F64, dict(
+            lat_lo=box[0], lat_hi=box[1], lon_lo=box[2], lon_hi=box[3], d_lat=d_lat, d_lon=d_lon, n_rows=n_rows,
+            n_cols=n_cols, crossing=int(crossing)))])
         counters = buf("counters", 3)
         table = buf("cells", 2 * n_rows * n_cols, torch.int64)
         _chk(self.lib.sw_store_grid(q.ctypes.data, _ptr(table), _ptr(counters), self._stream()), "sw_store_grid")
         cells = table[:2 * n_rows * n_cols].cpu().numpy().view(GRID_CELL).reshape(n_rows, n_cols)
-        info["candidates"], info["invalid"], info["outside"] = (int(x) for x in counters[:3].cpu().numpy().view(np.uint32))
+        info["candidates"], info["invalid"], info["outside"] = self._counters(counters, 3)
         cells["last_date"][cells["count"] == 0] = 0                              # the device leaves INT64_MIN there
         return cells, info
 
@@ -1600,8 +1602,7 @@ class GpuInboundEngine(EngineBase):
         sort_key = buf("sort", max(n_keys, 1), torch.int64)
         _chk(self.lib.sw_store_rank(q.ctypes.data, _ptr(tab), _ptr(table), _ptr(sort_key), _ptr(counters),
                                     self._stream()), "sw_store_rank")
-        info["candidates"], info["nan"], info["ungrouped"], groups = (
-            int(x) for x in counters[:4].cpu().numpy().view(np.uint32))
+        info["candidates"], info["nan"], info["ungrouped"], groups = self._counters(counters, 4)
         info["groups"] = groups
         # stable sorts, least significant key first: key asc, then the statistic
         rows = table[:7 * groups].view(-1, 7)

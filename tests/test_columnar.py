@@ -88,5 +88,8 @@ def test_ring_view_heads_the_hot_store_queries():
     assert "static_assert(sizeof(SwRingView) == %d" % (8 * len(RING_QUERY)) in text
     for words, name, size in ((SERIES_QUERY, "SwSeriesQuery", 144), (NEAR_QUERY, "SwNearQuery", 176)):
         assert words[:len(RING_QUERY)] == RING_QUERY and len(set(words)) == len(words)
-        assert re.search(r"typedef struct %s \{\s*SwRingView \w+;" % name, text)       # the view is the first member
+        # the view is the first member, of the query or of the position view that is the query's first
+        first = re.search(r"typedef struct %s \{\s*(\w+) \w+;" % name, text).group(1)
+        assert first == ("SwPositionView" if name == "SwNearQuery" else "SwRingView")
+        assert re.search(r"typedef struct SwPositionView \{\s*SwRingView \w+;", text)
         assert 8 * len(words) == size and "static_assert(sizeof(%s) == %d" % (name, size) in text

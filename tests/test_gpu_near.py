@@ -12,7 +12,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="n
 if gpu_available():
     from sitewhere_amd.pipeline.gpu_engine import GpuInboundEngine
 
-from sitewhere_amd.models.columnar import EV_LOCATION, EV_MEASUREMENT, NEAR_QUERY
+from sitewhere_amd.models.columnar import EV_LOCATION, EV_MEASUREMENT, NEAR_QUERY, NEAR_QUERY_F64, NEAR_WORDS, RING_QUERY
 from sitewhere_amd.pipeline.cpu_engine import CpuInboundEngine
 from sitewhere_amd.pipeline.near import NEAR_BAND_M
 
@@ -109,10 +109,24 @@ def test_empty_ring_and_refused_arguments_launch_nothing():
     # a query nothing matches: counted on the device, an empty page
     total, cols, eids, dist, info = g.near_store(-33.5, 95.5, 1000.0)
     assert total == 0 and len(eids) == len(dist) == 0 and info["candidates"] > 0 and "near" in g._ring_bufs
+    # a view the engine never builds, its oldest row one past the ring: the entry point itself refuses it
+    # (hipErrorInvalidValue) before the counters of the query above are zeroed
+    _, n, head, bits, _ = g._position_view("near", None, None, None, False)
+    head[RING_QUERY.index("head")] = n
+    q = np.concatenate([head, g._query_words(NEAR_WORDS, NEAR_QUERY_F64, dict(
+        lat=0.0, lon=0.0, radius_m=1.0, lat_lo=-1.0, lat_hi=1.0, lon_lo=-1.0, lon_hi=1.0))])
+    rows, dist, counters = (g._ring_bufs["near"][k] for k in ("rows", "dist", "counters"))
+    before = counters[:3].cpu()
+    assert g.lib.sw_store_near(q.ctypes.data, rows.data_ptr(), dist.data_ptr(), rows.numel(), counters.data_ptr(),
+                               g._stream()) == 1
+    assert counters[:3].cpu().tolist() == before.tolist() and before[1] > 0
 
 
 def test_match_buffers_grow_and_the_pass_repeats():
     g, c, _ = ring_pair(1 << 14)
+    g._near_rows0 = 64                                 # fewer than the 180 latest rows: the best passes run twice
+    check(g, c, lat=CENTRE[0], lon=CENTRE[1], radius_m=250000.0, latest=True, page_size=0)
+    assert g._ring_bufs["near"]["rows"].numel() == g._ring_bufs["near"]["dist"].numel() == 180
     g._near_rows0 = 256                                # fewer rows than the 925 and 1914 matches below
     check(g, c, lat=CENTRE[0], lon=CENTRE[1], radius_m=60000.0, order="distance", page_size=0)
     assert g._ring_bufs["near"]["rows"].numel() == g._ring_bufs["near"]["dist"].numel() == 925
@@ -126,6 +140,7 @@ def test_abi_size_of_the_query():
     from sitewhere_amd._native import gpu
     from sitewhere_amd.ops.engine_abi import abi_sizes
     assert abi_sizes(gpu())["near_query"] == 8 * len(NEAR_QUERY) == 176
+    assert abi_sizes(gpu())["position_view"] == 120
 
 
 def as_bytes(r):

@@ -106,6 +106,9 @@ def test_empty_ring_and_refused_arguments_launch_nothing():
 
 def test_match_buffer_grows_and_the_pass_repeats():
     g, c = ring_pair(1 << 14)
+    g._zone_rows0 = 64                                 # fewer than the 180 latest rows: the best passes run twice
+    check(g, c, polygon=POLYGONS["world"], latest=True, page_size=0)
+    assert g._ring_bufs["zone"]["rows"].numel() == 180
     g._zone_rows0 = 256                                # fewer rows than the 707 and 1914 matches below
     check(g, c, polygon=POLYGONS["ell"], page_size=0)
     assert g._ring_bufs["zone"]["rows"].numel() == EXPECTED[1 << 14]["ell"][0] == 707

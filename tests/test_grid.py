@@ -1,18 +1,18 @@
 """Location density grids (``EngineBase.grid_store``) on the CPU engines -- the oracle of the MI355X
 kernel (tests/test_gpu_grid.py) -- and through the service API, the search provider and REST."""
 import math
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from sitewhere_amd.models.columnar import GRID_CELL, GRID_QUERY, GRID_QUERY_F64, NEAR_QUERY, RING_QUERY, ZONE_QUERY
+from sitewhere_amd.models.columnar import (GRID_CELL, GRID_QUERY, GRID_QUERY_F64, NEAR_QUERY, POSITION_QUERY, RING_QUERY,
+                                           ZONE_QUERY)
 from sitewhere_amd.pipeline.cpu_engine import CpuInboundEngine
 from sitewhere_amd.pipeline.grid import (GRID_MAX_CELLS, check_grid_args, grid_cell_np, grid_select, grid_steps,
                                          host_grid)
 from sitewhere_amd.pipeline.native_engine import NativeCpuEngine
 
+from abi_header import HEADER, struct_fields
 from grid_scenarios import (AROUND, BOXES, CROSSING, CUT, HAND_INFO, assert_conserved, assert_same_grid,
                             brute_force_grid, case_queries, hand_expected, hand_grid_batch)
 from near_scenarios import RINGS
@@ -20,7 +20,6 @@ from pipeline_scenarios import NOW, setup_fleet, small_cfg
 from series_scenarios import fill_ring
 from test_near import HOME, T0, _north, site  # noqa: F401  (the instance with a hot tenant and a per-event one)
 
-HEADER = Path(__file__).resolve().parent.parent / "csrc" / "include" / "swengine.h"
 GRIDS = [("around", 1, 1), ("around", 8, 8), ("cut", 3, 5), ("crossing", 8, 8), ("crossing", 3, 5), ("around", 1, 300)]
 
 
@@ -170,35 +169,20 @@ def test_host_grid_equals_the_oracle(rings):
         host_grid(evs, 34.0, 33.0, -85.0, -84.0, 2, 2)
 
 
-def _struct_fields(name):
-    text = re.sub(r"//[^\n]*", "", HEADER.read_text())
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        if decl.strip():
-            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(.+)", decl.strip(), re.S)
-            assert m, f"unparsed declaration in {name}: {decl!r}"
-            if m.group(1) == "SwRingView":                     # the shared head, by value: its words come first
-                fields += _struct_fields("SwRingView")[1]
-                continue
-            for f in m.group(3).split(","):
-                fields.append((f.strip(), "ptr" if m.group(2) else m.group(1)))
-    return text, fields
-
-
 def test_grid_query_mirrors_header():
-    text, fields = _struct_fields("SwGridQuery")
+    text, fields = struct_fields("SwGridQuery")
     assert tuple(n for n, _ in fields) == GRID_QUERY and len(GRID_QUERY) == 24 and GRID_QUERY[:10] == RING_QUERY
     assert {t for _, t in fields} == {"ptr", "int64_t", "double"}                  # every field 8 bytes
     assert tuple(n for n, t in fields if t == "double") == GRID_QUERY_F64
     assert "static_assert(sizeof(SwGridQuery) == %d" % (8 * len(GRID_QUERY)) in text
     assert "#define SW_GRID_MAX_CELLS %d" % GRID_MAX_CELLS in text
-    assert [n for n, _ in _struct_fields("SwGridCell")[1]] == list(GRID_CELL.names) and GRID_CELL.itemsize == 16
-    # the other queries' layouts are as they were: the three share k_near_best through the same member names
-    assert tuple(n for n, _ in _struct_fields("SwNearQuery")[1]) == NEAR_QUERY
-    assert tuple(n for n, _ in _struct_fields("SwZoneQuery")[1]) == ZONE_QUERY
-    for shared in ("v0", "v1", "latest", "best_date", "best_seq"):
-        assert shared in GRID_QUERY and shared in NEAR_QUERY
+    assert [n for n, _ in struct_fields("SwGridCell")[1]] == list(GRID_CELL.names) and GRID_CELL.itemsize == 16
+    # the other queries' layouts mirror the header too: the three share k_near_best through one head, SwPositionView
+    assert tuple(n for n, _ in struct_fields("SwNearQuery")[1]) == NEAR_QUERY
+    assert tuple(n for n, _ in struct_fields("SwZoneQuery")[1]) == ZONE_QUERY
+    assert NEAR_QUERY[:15] == ZONE_QUERY[:15] == GRID_QUERY[:15] == POSITION_QUERY
+    assert tuple(n for n, _ in struct_fields("SwPositionView")[1]) == POSITION_QUERY
+    assert "static_assert(sizeof(SwPositionView) == %d" % (8 * len(POSITION_QUERY)) in text
     # sw_abi_sizes reports the size the library was compiled with (compared on the GPU in
     # tests/test_gpu_grid.py, where the library loads): here, that the word it reports is this struct's
     assert "out[15] = sizeof(SwGridQuery);" in (HEADER.parent.parent / "hip" / "swgpu.hip").read_text()

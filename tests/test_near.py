@@ -1,8 +1,6 @@
 """Locations near a point (``EngineBase.near_store``) on the CPU engines -- the oracle of the MI355X
 kernels (tests/test_gpu_near.py) -- and through the service API, the search provider and REST."""
 import math
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -14,12 +12,11 @@ from sitewhere_amd.pipeline.native_engine import NativeCpuEngine
 from sitewhere_amd.pipeline.near import (NEAR_BAND_M, NEAR_MAX_RADIUS_M, check_near_args, haversine_np, host_near,
                                          in_box, near_box)
 
+from abi_header import HEADER, struct_fields
 from pipeline_scenarios import NOW, setup_fleet, small_cfg
 from near_scenarios import (CENTRE, HAND_QUERIES, RADII, RINGS, assert_clear_of_band, brute_force_near, case_queries,
                             hand_near_batch)
 from series_scenarios import fill_ring
-
-HEADER = Path(__file__).resolve().parent.parent / "csrc" / "include" / "swengine.h"
 
 
 @pytest.fixture(scope="module", params=sorted(RINGS))
@@ -178,24 +175,8 @@ def test_host_near_matches_the_oracle():
     assert host_near([], 0, 0, 1) == {"hotSince": None, "numResults": 0, "results": [], "distances": []}
 
 
-def _struct_fields(name):
-    text = re.sub(r"//[^\n]*", "", HEADER.read_text())
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        if decl.strip():
-            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(.+)", decl.strip(), re.S)
-            assert m, f"unparsed declaration in {name}: {decl!r}"
-            if m.group(1) == "SwRingView":                     # the shared head, by value: its words come first
-                fields += _struct_fields("SwRingView")[1]
-                continue
-            for f in m.group(3).split(","):
-                fields.append((f.strip(), "ptr" if m.group(2) else m.group(1)))
-    return text, fields
-
-
 def test_near_query_mirrors_header():
-    text, fields = _struct_fields("SwNearQuery")
+    text, fields = struct_fields("SwNearQuery")
     assert tuple(n for n, _ in fields) == NEAR_QUERY
     assert {t for _, t in fields} == {"ptr", "int64_t", "double"}                  # every field 8 bytes
     assert tuple(n for n, t in fields if t == "double") == NEAR_QUERY_F64

@@ -1,8 +1,6 @@
 """Rankings of groups over the event ring (``EngineBase.rank_store``) on the CPU engines -- the oracle of
 the MI355X kernels (tests/test_gpu_rank.py) -- and through the service API, the search provider and REST."""
 import math
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ from sitewhere_amd.pipeline.cpu_engine import CpuInboundEngine
 from sitewhere_amd.pipeline.native_engine import NativeCpuEngine
 from sitewhere_amd.pipeline.rank import check_rank_args, host_rank, rank_key, rank_select
 
+from abi_header import HEADER, struct_fields
 from near_scenarios import RINGS
 from pipeline_scenarios import NOW, small_cfg
 from rank_scenarios import (COLUMN, GROUPS, HAND_ALERT_ASG, HAND_ROWS, KEY_SETS, RING_FACTS, TEMP, assert_conserved,
@@ -20,8 +19,6 @@ from rank_scenarios import (COLUMN, GROUPS, HAND_ALERT_ASG, HAND_ROWS, KEY_SETS,
                             hand_rank_fleet, ring_queries, total_order_key)
 from series_scenarios import NAMES, fill_ring
 from test_near import T0, site  # noqa: F401  (the instance with a hot tenant and a per-event one)
-
-HEADER = Path(__file__).resolve().parent.parent / "csrc" / "include" / "swengine.h"
 
 
 @pytest.fixture(scope="module")
@@ -217,29 +214,13 @@ def test_host_rank_equals_the_oracle(rings):
         host_rank([], EV_MEASUREMENT, "assignment", "max")
 
 
-def _struct_fields(name):
-    text = re.sub(r"//[^\n]*", "", HEADER.read_text())
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        if decl.strip():
-            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(.+)", decl.strip(), re.S)
-            assert m, f"unparsed declaration in {name}: {decl!r}"
-            if m.group(1) == "SwRingView":                     # the shared head, by value: its words come first
-                fields += _struct_fields("SwRingView")[1]
-                continue
-            for f in m.group(3).split(","):
-                fields.append((f.strip(), "ptr" if m.group(2) else m.group(1)))
-    return text, fields
-
-
 def test_rank_query_and_cell_mirror_the_header():
-    text, fields = _struct_fields("SwRankQuery")
+    text, fields = struct_fields("SwRankQuery")
     assert tuple(n for n, _ in fields) == RANK_QUERY and len(RANK_QUERY) == 20 and RANK_QUERY[:10] == RING_QUERY
     assert {t for _, t in fields} == {"ptr", "int64_t"}                            # every field 8 bytes
     assert "static_assert(sizeof(SwRankQuery) == %d" % (8 * len(RANK_QUERY)) in text
     assert "#define SW_RANK_MAX_KEYS (1 << 22)" in text and RANK_MAX_KEYS == 1 << 22
-    cell = _struct_fields("SwRankCell")[1]
+    cell = struct_fields("SwRankCell")[1]
     assert [n for n, _ in cell] == list(RANK_CELL.names) and RANK_CELL.itemsize == 56 == 8 * len(cell)
     assert [t == "double" for _, t in cell] == [RANK_CELL[n].kind == "f" for n in RANK_CELL.names]
     assert "out[16] = sizeof(SwRankQuery);" in (HEADER.parent.parent / "hip" / "swgpu.hip").read_text()

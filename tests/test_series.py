@@ -1,8 +1,5 @@
 """Measurement series in time buckets (``EngineBase.aggregate_store``) on the CPU engines -- the oracle
 of the MI355X kernels (tests/test_gpu_series.py) -- and through the service API and REST."""
-import re
-from pathlib import Path
-
 import numpy as np
 import pytest
 
@@ -11,10 +8,9 @@ from sitewhere_amd.pipeline.cpu_engine import CpuInboundEngine
 from sitewhere_amd.pipeline.fleet import hash64
 from sitewhere_amd.pipeline.native_engine import NativeCpuEngine
 
+from abi_header import struct_fields
 from pipeline_scenarios import NOW, setup_fleet, small_cfg
 from series_scenarios import CASES, NAMES, assert_cells, brute_force, fill_ring, hand_series_batch
-
-HEADER = Path(__file__).resolve().parent.parent / "csrc" / "include" / "swengine.h"
 
 
 @pytest.mark.parametrize("cls", [CpuInboundEngine, NativeCpuEngine])
@@ -50,30 +46,14 @@ def test_oracle_matches_brute_force_on_wrapped_ring(cls):
     assert eng.aggregate_store(*CASES[4][:5])[0].size == 32008
 
 
-def _struct_fields(name):
-    text = re.sub(r"//[^\n]*", "", HEADER.read_text())
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        if decl.strip():
-            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(.+)", decl.strip(), re.S)
-            assert m, f"unparsed declaration in {name}: {decl!r}"
-            if m.group(1) == "SwRingView":                     # the shared head, by value: its words come first
-                fields += _struct_fields("SwRingView")[1]
-                continue
-            for f in m.group(3).split(","):
-                fields.append((f.strip(), "ptr" if m.group(2) else m.group(1)))
-    return text, fields
-
-
 def test_series_cell_mirrors_header():
-    text, fields = _struct_fields("SwSeriesCell")
+    text, fields = struct_fields("SwSeriesCell")
     kinds = {"int64_t": np.dtype("<i8"), "double": np.dtype("<f8")}
     assert [(n, kinds[t]) for n, t in fields] == [(n, SERIES_CELL.fields[n][0]) for n in SERIES_CELL.names]
     assert [SERIES_CELL.fields[n][1] for n in SERIES_CELL.names] == list(range(0, 80, 8))
     assert SERIES_CELL.itemsize == 80 and "static_assert(sizeof(SwSeriesCell) == 80" in text
     # the query block the host builds as int64 words: same names, same order, every field 8 bytes
-    _, qf = _struct_fields("SwSeriesQuery")
+    _, qf = struct_fields("SwSeriesQuery")
     assert tuple(n for n, _ in qf) == SERIES_QUERY
     assert {t for _, t in qf} == {"ptr", "int64_t"}
 

@@ -1,27 +1,24 @@
 """Locations in a zone (``EngineBase.zone_store``) on the CPU engines -- the oracle of the MI355X
 kernel (tests/test_gpu_zone.py) -- and through the service API, the search provider and REST."""
 import math
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from sitewhere_amd.core.geo import contains, polygon_of
-from sitewhere_amd.models.columnar import NEAR_QUERY, ZONE_QUERY, ZONE_QUERY_F64
+from sitewhere_amd.models.columnar import GRID_QUERY, NEAR_QUERY, POSITION_QUERY, ZONE_QUERY, ZONE_QUERY_F64
 from sitewhere_amd.pipeline.cpu_engine import CpuInboundEngine
 from sitewhere_amd.pipeline.native_engine import NativeCpuEngine
 from sitewhere_amd.pipeline.zone import (ZONE_MAX_VTX, check_zone_args, contains_np, host_zone, in_zone_box, zone_box,
                                          zone_select)
 
+from abi_header import HEADER, struct_fields
 from pipeline_scenarios import NOW, setup_fleet, small_cfg
 from near_scenarios import RINGS, SUB_RANGE, SUBSET, hand_near_batch
 from series_scenarios import fill_ring
 from test_near import HOME, T0, _north, site  # noqa: F401  (the instance with a hot tenant and a per-event one)
 from zone_scenarios import (EXPECTED, HAND_INFO, HAND_RECTS, POLYGONS, assert_same_zone_answer, brute_force_zone,
                             case_queries, expected_total, inside_flags, rect)
-
-HEADER = Path(__file__).resolve().parent.parent / "csrc" / "include" / "swengine.h"
 
 
 @pytest.fixture(scope="module")
@@ -196,33 +193,16 @@ def test_host_zone_matches_the_oracle(rings):
     assert sel.tolist() == [2, 0] and bad == 1
 
 
-def _struct_fields(name):
-    text = re.sub(r"//[^\n]*", "", HEADER.read_text())
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        if decl.strip():
-            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(.+)", decl.strip(), re.S)
-            assert m, f"unparsed declaration in {name}: {decl!r}"
-            if m.group(1) == "SwRingView":                     # the shared head, by value: its words come first
-                fields += _struct_fields("SwRingView")[1]
-                continue
-            for f in m.group(3).split(","):
-                fields.append((f.strip(), "ptr" if m.group(2) else m.group(1)))
-    return text, fields
-
-
 def test_zone_query_mirrors_header():
-    text, fields = _struct_fields("SwZoneQuery")
+    text, fields = struct_fields("SwZoneQuery")
     assert tuple(n for n, _ in fields) == ZONE_QUERY and len(ZONE_QUERY) == 22
     assert {t for _, t in fields} == {"ptr", "int64_t", "double"}                  # every field 8 bytes
     assert tuple(n for n, t in fields if t == "double") == ZONE_QUERY_F64
     assert "static_assert(sizeof(SwZoneQuery) == %d" % (8 * len(ZONE_QUERY)) in text
     assert "#define SW_ZONE_MAX_VTX %d" % ZONE_MAX_VTX in text
-    # the near query's layout is as it was: the two share k_near_best through the same member names
-    assert tuple(n for n, _ in _struct_fields("SwNearQuery")[1]) == NEAR_QUERY
-    for shared in ("v0", "v1", "latest", "best_date", "best_seq"):
-        assert shared in ZONE_QUERY and shared in NEAR_QUERY
+    # the near query's layout mirrors the header too: the queries share k_near_best through one head, SwPositionView
+    assert tuple(n for n, _ in struct_fields("SwNearQuery")[1]) == NEAR_QUERY
+    assert NEAR_QUERY[:15] == ZONE_QUERY[:15] == GRID_QUERY[:15] == POSITION_QUERY
     # sw_abi_sizes reports the size the library was compiled with (compared on the GPU in
     # tests/test_gpu_zone.py, where the library loads): here, that the word it reports is this struct's
     assert "out[14] = sizeof(SwZoneQuery);" in (HEADER.parent.parent / "hip" / "swgpu.hip").read_text()
