@@ -2705,6 +2705,13 @@ __global__ void k_cl_prep(const uint32_t* __restrict__ ok_idx, const uint32_t* _
 // load per id instead of four 16-byte loads by one thread), a hit anywhere ends the id, else the lowest
 // lane holding a free slot claims it with one CAS (another id winning the slot: the group looks
 // again); a full bucket sends the id on to the next.  The bucket rule of ff_add.
+// The drop rule is not literally ff_add's: the loop is bounded at 2 * SW_FF_MAX_PROBE rounds and a lost
+// CAS is a round too.  An id whose chain has SW_FF_MAX_PROBE full buckets (1024 ids that share a run of
+// buckets in one generation) and that lost no CAS goes on to bucket SW_FF_MAX_PROBE + 1 and beyond,
+// where ff_add drops it and no probe looks for it; one that lost more than SW_FF_MAX_PROBE CASes on
+// its way (as many ids racing for one run of buckets in one step) is dropped with room left inside the
+// bound.  Both need about a thousand ids of one step or generation in one run of buckets, far from
+// what a table at load <= 1/2 sees; tests/test_gpu_dedup.py stays below it on purpose.
 __global__ __launch_bounds__(BLK) void k_ff_add_rows(SwEngineArgs a, const SwEventRec* __restrict__ R,
                                                      const uint32_t* __restrict__ idx,
                                                      const uint32_t* __restrict__ n_ptr, uint32_t cap) {

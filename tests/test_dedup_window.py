@@ -4,7 +4,9 @@ Pushes far more distinct alternate ids than the window holds (several generation
 Python oracle and the native engine -- and the MI355X engine when present -- with replays of recent
 batches (inside the window: duplicates) and of old ones (retired generations: new again).  All
 engines must agree event for event, the window must actually rotate, and nothing may overflow
-silently (``dedup_overflow`` stays 0)."""
+silently (``dedup_overflow`` stays 0).  At this load probes hardly ever chain: full filter buckets,
+window chains across the table end, other generation counts and many copies of one id in a batch
+are in ``tests/test_dedup_chains.py`` and ``tests/test_gpu_dedup.py``."""
 from __future__ import annotations
 
 import numpy as np
